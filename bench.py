@@ -19,7 +19,14 @@ is timed and reported (`gather`).  No collective touches the data path.  Rank 0 
 the in-process N-device product path (`e2e`: lzbench_hip_compress_batch / _decompress_batch with
 ngpus = N over the N shards' bytes, what `lzbench_hip -gN` runs).
 
-Also reported (rank 0):
+A plain run (no --full) sets up, warms up, times --steps steps and prints the result line: value, ms_per_step
+(wall milliseconds per timed step), ratio_pct and the per-stage milliseconds of the HIP events the timed steps record
+anyway.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).  The gather, the e2e rows
+and everything in the list below run only with --full, after the timed region; --no-cpu-baseline and --no-e2e
+leave those two out of a --full run.
+
+With --full, also reported (rank 0):
+  roundtrip_ok                    the decoded bytes equal the input, every chunk's status >= 0
   roofline / roofline_decompress  the codec kernels, HIP events on the stream they run on
   bit_exact                       the whole packed stream + compr_sizes vs the reference digest
                                   (tests/golden/fullsize.json) when the workload has one
@@ -265,6 +272,36 @@ def e2e_rows(L, host, codec, chunk, level, ngpus, iters, dig=None):
     }
 
 
+DUMP_SAMPLE = 4 << 20       # sampled byte positions per large output (float32: 16 MiB each)
+
+
+def dump_outputs(outdir, codec, comp_total, n, chunk, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the packed stream, its
+    compr_sizes, the decoded bytes and the per-chunk decode status -- as DIR/<name>.npy (float64, the byte samples
+    float32; about 33 MiB in all).  The two byte arrays are too large to store whole: each is stored as the bytes at
+    DUMP_SAMPLE positions drawn by a fixed-seed generator (the same positions in every run of the same arguments and
+    the same output size), plus the byte sum of every chunk, which covers every byte.  The input is the seeded
+    corpus, so two builds run with the same arguments can be compared file by file.  At N > 1 rank r writes
+    <name>_rank<r>.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    k = int(codec.k)
+    offs = codec.offsets[:k + 1].cpu().numpy().astype(np.int64)
+    packed = codec.packed[:comp_total].cpu().numpy()
+    out = codec.out[:n].cpu().numpy()
+    rng = np.random.default_rng(20240531)
+    arrays = {
+        "packed_total": np.array([comp_total], np.float64),
+        "compr_sizes": codec.csizes[:k].cpu().numpy().astype(np.float64),
+        "status": codec.status[:k].cpu().numpy().astype(np.float64),
+        "packed_chunk_sums": np.add.reduceat(packed, offs[:k], dtype=np.uint64).astype(np.float64) * (np.diff(offs) > 0),
+        "out_chunk_sums": np.add.reduceat(out, np.arange(0, n, chunk), dtype=np.uint64).astype(np.float64),
+        "packed_sample": packed[np.sort(rng.integers(0, max(comp_total, 1), DUMP_SAMPLE))].astype(np.float32),
+        "out_sample": out[np.sort(rng.integers(0, n, DUMP_SAMPLE))].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,6 +316,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--backend", default="gloo", help="control-plane process group (no data-path collective)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure (the docstring's 'With --full' list)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -359,8 +400,62 @@ def main():
     d_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in timed]))
     comp_total = codec.packed_total()
     k_chunks = int(codec.k)
-    roundtrip_ok = bool(torch.equal(codec.out[:n], d_in[:n])) and bool((codec.status >= 0).all().item())
     ratio = comp_total / n
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, codec, comp_total, n, chunk, rank, world)
+
+    total_bytes = world * n * args.steps
+    value = total_bytes / elapsed / 1e6
+    res = {
+        "metric": metric_for(args.codec, args.chunk_kib, n, args.corpus, args.level),
+        "value": round(value, 2),
+        "unit": "MB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": f"synthetic {args.corpus} corpus (SURVEY.md 8(d) stand-in; enwik8/Silesia unavailable offline): "
+                f"rank r owns share r ({size_label(n)}) of one {size_label(world * n)} seed-12345 corpus, resident in HBM",
+        "config": {
+            "workload": f"{args.codec}{',' + str(args.level) if args.codec in ('lz4fast', 'zstd') else ''} "
+                        f"-b{args.chunk_kib} on {size_label(n)} {args.corpus} per GPU, comp+decomp pass",
+            "codec": args.codec,
+            "chunk_kib": args.chunk_kib,
+            "bytes_per_gpu": n,
+            "chunks_per_gpu": k_chunks,
+            "parallelism": f"chunk-sharded x{world} (contiguous shard per GPU, host-side gather, no collective)",
+        },
+        "ratio_pct": round(100 * ratio, 3),
+        "comp_MBps": round(n / ((k_ms + x_ms + f_ms) * 1e-3) / 1e6, 2),
+        "decomp_MBps": round(n / (d_ms * 1e-3) / 1e6, 2),
+        "stage_ms": {"compress_kernel": round(k_ms, 3), "emit_kernel": round(x_ms, 3), "scan_pack": round(f_ms, 3),
+                     "decompress": round(d_ms, 3)},
+    }
+    if args.full:
+        timed_path = [codec, d_in]     # handed over: full_report frees these device buffers before its e2e rows
+        del codec, d_in, step
+        res.update(full_report(args, L, dist, timed_path, host, rank, world, seed, comp_total, (k_ms, x_ms, f_ms, d_ms)))
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_report(args, L, dist, timed_path, host, rank, world, seed, comp_total, stage_ms):
+    """--full: the checks and measurements beside the headline figure, as result fields (the docstring's list).
+    Runs after the timed region.  timed_path: [DeviceCodec, input tensor] of the timed steps, the only references
+    to them; the list is emptied before the e2e rows so that their device memory is free."""
+    import torch
+    codec, d_in = timed_path
+    n = args.size_mib << 20
+    chunk = args.chunk_kib << 10
+    k_ms, x_ms, f_ms, d_ms = stage_ms
+    roundtrip_ok = bool(torch.equal(codec.out[:n], d_in[:n])) and bool((codec.status >= 0).all().item())
 
     result_extra = {}
     whole = fullsize_digest(args.corpus, args.codec, chunk, args.level, world * n, seed) if world > 1 else None
@@ -414,6 +509,7 @@ def main():
         # (host memory on rank 0: the N-copy input plus its packed output and the decode buffer, about
         # 3N GiB at the default 1 GiB per GPU -- 24 GiB at N = 8, well inside a node's RAM)
         del d_in, codec
+        timed_path.clear()
         torch.cuda.empty_cache()
         if dist:
             dist.barrier()
@@ -428,8 +524,6 @@ def main():
     achieved = algo_bytes / (k_ms * 1e-3) / 1e9
     dec_achieved = algo_bytes / (d_ms * 1e-3) / 1e9   # decompress reads C, writes N
     wkey = f"{args.codec}/{args.level}/{args.chunk_kib}/{args.corpus}/{n}"
-    total_bytes = world * n * args.steps
-    value = total_bytes / elapsed / 1e6
     kname = COMPRESS_KERNEL[args.codec]
     dname = DECOMPRESS_KERNEL.get(args.codec)
     if dname is None:   # LZ4 / snappy: the output-window variant the launcher picks for this many chunks
@@ -448,28 +542,6 @@ def main():
     tr_c, why_c = traffic_for(kname, wkey)
     tr_d, why_d = traffic_for(dname, wkey)
     res = {
-        "metric": metric_for(args.codec, args.chunk_kib, n, args.corpus, args.level),
-        "value": round(value, 2),
-        "unit": "MB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": f"synthetic {args.corpus} corpus (SURVEY.md 8(d) stand-in; enwik8/Silesia unavailable offline): "
-                f"rank r owns share r ({size_label(n)}) of one {size_label(world * n)} seed-12345 corpus, resident in HBM",
-        "config": {
-            "workload": f"{args.codec}{',' + str(args.level) if args.codec in ('lz4fast', 'zstd') else ''} "
-                        f"-b{args.chunk_kib} on {size_label(n)} {args.corpus} per GPU, comp+decomp pass",
-            "codec": args.codec,
-            "chunk_kib": args.chunk_kib,
-            "bytes_per_gpu": n,
-            "chunks_per_gpu": k_chunks,
-            "parallelism": f"chunk-sharded x{world} (contiguous shard per GPU, host-side gather, no collective)",
-        },
         "roofline": {
             "bound": "hbm",
             "achieved": round(achieved, 2),
@@ -505,19 +577,10 @@ def main():
             "kernel_ms": round(d_ms, 3),
         },
         "cpu_baseline": cpu,
-        "ratio_pct": round(100 * ratio, 3),
-        "comp_MBps": round(n / ((k_ms + x_ms + f_ms) * 1e-3) / 1e6, 2),
-        "decomp_MBps": round(n / (d_ms * 1e-3) / 1e6, 2),
-        "stage_ms": {"compress_kernel": round(k_ms, 3), "emit_kernel": round(x_ms, 3), "scan_pack": round(f_ms, 3),
-                     "decompress": round(d_ms, 3)},
         "roundtrip_ok": roundtrip_ok,
     }
     res.update(result_extra)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return res
 
 
 if __name__ == "__main__":
