@@ -151,6 +151,46 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
                          const uint64_t* d_offsets, size_t n, size_t chunk_size, void* d_out, int32_t* d_status,
                          void* d_temp, size_t temp_bytes, void* hip_stream);
 
+/* ---- 3b. ragged batches ---------------------------------------------------------------- */
+/* The calls above with per-chunk pointers and sizes (the shape of the reference's batched calls,
+ * nvcomp/lz4.h:292-371) in place of one buffer cut at a chunk size: chunk i is the d_in_bytes[i] bytes at
+ * d_in_ptrs[i], any alignment, chunks may overlap or repeat.  d_in_ptrs, d_in_bytes, d_out_ptrs and
+ * d_out_bytes are device arrays of nchunks entries; nothing here synchronises with the host or reads a size
+ * back, so the calls can be captured in a stream like the uniform ones.
+ * Codecs: LZH_CODEC_LZ4 (level = acceleration, as above) and LZH_CODEC_SNAPPY; zstd, the LZ4 frame, the
+ * nvcomp container and memcpy return LZH_EARG for now (so do their sizing functions: 0).
+ * Output: as the uniform compress call writes it -- d_csizes[i], d_offsets[0 .. nchunks] ([nchunks] = the packed
+ * total), chunks packed contiguously in index order, a chunk whose compressed size equals its size stored raw; equal
+ * sizes over contiguous inputs give the uniform call's bytes.  A zero-length chunk is legal (the one-byte LZ4
+ * block / snappy varint).  nchunks == 0 returns LZH_OK and launches nothing.
+ * Readable slack: every input chunk needs 16 readable bytes after it (the uniform calls' in_readable >= n + 16);
+ * the kernels address a chunk through a buffer descriptor of its size + 16 and read nothing past that.
+ * max_chunk_bytes bounds every d_in_bytes[i] / d_out_bytes[i]; at most 16 MiB (the sequence records' limit),
+ * else LZH_EARG.  A chunk whose device-side size is larger is not processed: compression gives d_csizes[i] = 0
+ * (it takes no packed bytes), decompression d_status[i] = -1; no kernel touches that chunk's slots.
+ * packed_cap: the sizes are only known on the device, so the capacity is enforced there, as the uniform pack does:
+ * a chunk whose packed range would pass packed_cap is not written, d_csizes and d_offsets still report every size,
+ * and d_offsets[nchunks] > packed_cap tells the caller that the output is incomplete.
+ * lzh_ragged_max_packed_bytes is the capacity no batch of that total size and chunk count exceeds.
+ * Temp: nchunks staging slots, then nchunks sequence-record slots, each sized for max_chunk_bytes (compress);
+ * scanned offsets and nchunks 32-byte block descriptors (decompress).  One large chunk therefore makes every
+ * slot large: a skewed batch pays nchunks x the largest chunk in temp (size-binned slots would not; not done).
+ * Checks (codec, max_chunk_bytes, null pointers, then temp_bytes below the sizing answer: LZH_ESPACE) come
+ * before any device call; the sizing functions are host arithmetic.
+ * d_offsets of the decompress call may be NULL (derived from d_csizes into d_temp).  d_status[i]: decoded
+ * size of chunk i, negative on malformed input, as above. */
+size_t lzh_ragged_compress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_ragged_decompress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchunks);
+int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                              size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                              void* hip_stream);
+int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                size_t temp_bytes, void* hip_stream);
+
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */
 int lzh_compress_kernel_only(int codec, int level, const void* d_in, size_t n, size_t in_readable,

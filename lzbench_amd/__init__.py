@@ -22,7 +22,7 @@ import numpy as np
 
 __all__ = [
     "ExtensionMissing", "lib", "CODECS", "COMP_DESC", "CompressorDesc", "find_compressor",
-    "compress_chunks", "decompress_chunks", "chunk_sizes_for", "datagen", "DeviceCodec",
+    "compress_chunks", "decompress_chunks", "chunk_sizes_for", "datagen", "DeviceCodec", "RaggedCodec",
     "LZH_CODEC_LZ4", "LZH_CODEC_SNAPPY", "LZH_CODEC_MEMCPY", "LZH_CODEC_ZSTD", "LZH_CODEC_LZ4F", "LZH_CODEC_NVLZ4",
     "LZ4F_BLOCK_CHECKSUM", "LZ4F_CONTENT_CHECKSUM", "LZ4F_CONTENT_SIZE", "LZ4F_LINKED", "PAD_SIZE",
     "get_compress_bound",
@@ -94,6 +94,11 @@ SIGNATURES = {
     "lzh_debug_gather_order": (C.c_int, [_SZ, _P, _P, _P]),
     "lzh_compress_async": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_decompress_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
+    "lzh_ragged_decompress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
+    "lzh_ragged_max_packed_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
+    "lzh_compress_ragged_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_decompress_ragged_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_compress_kernel_only": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_kernel_stage": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
@@ -354,6 +359,99 @@ class DeviceCodec:
                                         self.dtemp.data_ptr(), self.dtemp.numel(), self._stream())
         if rc:
             raise RuntimeError(f"lzh_decompress_async failed ({rc})")
+
+    def packed_total(self) -> int:
+        return int(self.offsets[self.k].item())
+
+
+class RaggedCodec:
+    """Device-resident codec over ragged batches (include/lzbench_hip.h 3b): chunk i of a batch is
+    sizes[i] bytes at offsets[i] of a flat uint8 CUDA tensor, any alignment, in any order.
+
+    Buffers are sized once for max_chunks chunks of up to max_chunk_bytes (staging is per chunk at
+    the largest size: a skewed batch pays for its largest chunk max_chunks times); max_total_bytes
+    bounds a batch's total input (default max_chunks * max_chunk_bytes) and sizes `packed`.
+    Work is queued on torch's current stream; nothing synchronises with the host.
+    """
+
+    def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
+                 max_total_bytes: Optional[int] = None):
+        import torch
+        self.torch = torch
+        self.codec = CODECS[codec]
+        self.level = level if codec in _LEVELED else (1 if codec == "lz4" else 0)
+        self.max_chunk_bytes, self.max_chunks = max_chunk_bytes, max_chunks
+        self.max_total = max_chunks * max_chunk_bytes if max_total_bytes is None else max_total_bytes
+        L = lib()
+        ct = L.lzh_ragged_compress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
+        dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
+        if ct == 0 or dt == 0:
+            raise ValueError(f"ragged batches: codec {codec} / chunks of {max_chunk_bytes} bytes are not supported")
+        self.dev = device or torch.device("cuda", torch.cuda.current_device())
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        self.max_packed = L.lzh_ragged_max_packed_bytes(self.codec, self.max_total, max_chunks)
+        self.packed = torch.empty(self.max_packed + 64, **u8)
+        self.csizes = torch.empty(max_chunks, dtype=torch.int32, device=self.dev)
+        self.offsets = torch.empty(max_chunks + 1, dtype=torch.int64, device=self.dev)
+        self.status = torch.empty(max_chunks, dtype=torch.int32, device=self.dev)
+        self.ctemp = torch.empty(ct, **u8)
+        self.dtemp = torch.empty(dt, **u8)
+        self.k = 0
+
+    def _stream(self):
+        return self.torch.cuda.current_stream().cuda_stream
+
+    def _arrays(self, buf, offsets, sizes, slack):
+        """Device arrays (pointers, sizes) of a chunk list over buf, checked on the host."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        szs = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1)
+        if len(offs) != len(szs) or len(offs) > self.max_chunks:
+            raise ValueError("ragged batches: offsets / sizes mismatch or more chunks than max_chunks")
+        if len(offs) and (offs.min() < 0 or szs.min() < 0 or int((offs + szs).max()) + slack > buf.numel()):
+            raise ValueError(f"ragged batches: a chunk (with {slack} bytes of slack) passes the end of the buffer")
+        if int(szs.sum()) > self.max_total:
+            raise ValueError("ragged batches: more input than max_total_bytes")
+        both = np.stack([offs + buf.data_ptr(), szs])
+        d = self.torch.from_numpy(both).to(self.dev, non_blocking=False)
+        return d, len(offs)
+
+    def compress(self, buf, offsets, sizes) -> None:
+        """Compress chunks buf[offsets[i] : offsets[i] + sizes[i]] (each with 16 readable bytes after it inside
+        buf) into self.packed / csizes / offsets, as DeviceCodec.compress lays a uniform input out."""
+        self.compress_arrays(*self._arrays(buf, offsets, sizes, 16))
+
+    def compress_arrays(self, d, k: int) -> None:
+        """compress() on device arrays made before (d: int64 [2, k], chunk addresses and sizes): no host-to-device
+        copy, so the call can be captured in a graph."""
+        self._in = d   # (kept alive until the next call: the kernels read it asynchronously)
+        self.k = k
+        rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
+                                             self.max_chunk_bytes, self.packed.data_ptr(), self.packed.numel(),
+                                             self.csizes.data_ptr(), self.offsets.data_ptr(), self.ctemp.data_ptr(),
+                                             self.ctemp.numel(), self._stream())
+        if rc:
+            raise RuntimeError(f"lzh_compress_ragged_async failed ({rc})")
+
+    def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:
+        """Decode chunk i to out_buf[out_offsets[i] : out_offsets[i] + out_sizes[i]]; self.status[i] = its
+        decoded size or a negative verdict.  packed / csizes / offsets default to the last compress call's
+        (offsets=None with csizes given: derived on the device)."""
+        self.decompress_arrays(*self._arrays(out_buf, out_offsets, out_sizes, 0), packed, csizes, offsets)
+
+    def decompress_arrays(self, d, k: int, packed=None, csizes=None, offsets=None) -> None:
+        """decompress() on device arrays made before (d: int64 [2, k], output addresses and sizes)."""
+        if csizes is None and offsets is None:
+            offsets = self.offsets
+        packed = self.packed if packed is None else packed
+        csizes = self.csizes if csizes is None else csizes
+        self._out = d
+        self.k = k
+        rc = lib().lzh_decompress_ragged_async(self.codec, packed.data_ptr(), packed.numel(), csizes.data_ptr(),
+                                               offsets.data_ptr() if offsets is not None else None, d[0].data_ptr(),
+                                               d[1].data_ptr(), k, self.max_chunk_bytes, self.status.data_ptr(),
+                                               self.dtemp.data_ptr(), self.dtemp.numel(), self._stream())
+        if rc:
+            raise RuntimeError(f"lzh_decompress_ragged_async failed ({rc})")
 
     def packed_total(self) -> int:
         return int(self.offsets[self.k].item())

@@ -362,6 +362,89 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
     return LZH_OK;
 }
 
+// ---- 3b. ragged batches: chunk i = d_in_bytes[i] bytes at d_in_ptrs[i] (device arrays) ----
+// compress temp: nchunks staging slots | sequence records (nchunks record slots, then the per-chunk record
+// counts), all sized for max_chunk_bytes.  decompress temp: scanned offsets | nchunks block descriptors.
+
+static bool ragged_codec(int codec) { return codec == LZH_CODEC_LZ4 || codec == LZH_CODEC_SNAPPY; }
+
+size_t lzh_ragged_compress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks) {
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
+    size_t t = align_up(nchunks * lzh_stage_stride(codec, max_chunk_bytes), 256) + 256;
+    if (codec == LZH_CODEC_LZ4)
+        t += nchunks * lzh_lz4_rec_stride(max_chunk_bytes) + align_up(nchunks * 8, 256) + 256;
+    else
+        t += nchunks * lzh_snappy_rec_stride(max_chunk_bytes) +
+             align_up(nchunks * 4 * lzh_snappy_ragged_frags(max_chunk_bytes), 256) + 256;
+    return t;
+}
+
+size_t lzh_ragged_decompress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks) {
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
+    return align_up((nchunks + 1) * sizeof(uint64_t), 256) + 256 + align_up(nchunks * 32, 256) + 256;
+}
+
+size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchunks) {
+    // the sum of codec_bound over the chunks, whatever their sizes: the bounds are linear in the size but for
+    // their constant; then the uniform call's 8 bytes per chunk and 64
+    const size_t var = codec == LZH_CODEC_LZ4 ? total_in_bytes / 255 : codec == LZH_CODEC_SNAPPY ? total_in_bytes / 6 : 0;
+    return total_in_bytes + var + nchunks * (codec_bound(codec, 0) + 8) + 64;
+}
+
+int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                              size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                              void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
+    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
+    if (temp_bytes < lzh_ragged_compress_temp_bytes(codec, max_chunk_bytes, nchunks)) return LZH_ESPACE;
+    const uint32_t k = (uint32_t)nchunks;
+    const size_t stride = lzh_stage_stride(codec, max_chunk_bytes);
+    uint8_t* stage = (uint8_t*)d_temp;
+    uint8_t* recs = stage + align_up(nchunks * stride, 256) + 256;
+    {
+        Range range("lzh:compress_kernel");
+        if (codec == LZH_CODEC_LZ4)
+            LZH_CHECK(lzh_launch_lz4_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level, stage, stride,
+                                            d_csizes, k, recs, s));
+        else
+            LZH_CHECK(lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, k, recs, s));
+    }
+    Range range("lzh:scan_pack");
+    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
+    LZH_CHECK(lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, d_offsets,
+                                     (uint8_t*)d_packed, packed_cap, k, s));
+    return LZH_OK;
+}
+
+int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_packed || !d_csizes || !d_out_ptrs || !d_out_bytes || !d_status || !d_temp) return LZH_EARG;
+    if (nchunks > 0x7fffffffu) return LZH_EARG;
+    if (temp_bytes < lzh_ragged_decompress_temp_bytes(codec, max_chunk_bytes, nchunks)) return LZH_ESPACE;
+    Range range("lzh:decompress");
+    const uint64_t* offs = d_offsets;
+    if (!offs) {
+        LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)d_temp, nullptr, s));
+        offs = (const uint64_t*)d_temp;
+    }
+    void* desc = (uint8_t*)d_temp + align_up((nchunks + 1) * sizeof(uint64_t), 256) + 256;
+    LZH_CHECK(lzh_launch_ragged_desc(offs, d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes, desc, d_status,
+                                     (uint32_t)nchunks, s));
+    // (the block decoder adds the descriptor's destination, the chunk's address, to a null output base)
+    LZH_CHECK(lzh_launch_decompress(codec, (const uint8_t*)d_packed, packed_readable, nullptr, nullptr, 0, 0, nullptr,
+                                    d_status, (uint32_t)nchunks, s, desc));
+    return LZH_OK;
+}
+
 }  // extern "C"
 
 // ======================================================================= host layer

@@ -192,3 +192,15 @@ __device__ __forceinline__ bool block_span(uint64_t i, uint64_t n_total, uint64_
     n = (int)min(lim, n_total - off);
     return true;
 }
+
+// Chunk i of a ragged batch (device arrays of chunk pointers and sizes): loaded once, wave-uniform.
+// false = its size passes max_bytes (the batch's staging and record slots are sized for max_bytes: such a
+// chunk is not touched).  A chunk has 16 readable bytes after it.
+__device__ __forceinline__ bool ragged_span(const void* const* ptrs, const uint64_t* bytes, uint64_t i,
+                                            uint64_t max_bytes, const uint8_t*& p, int& n) {
+    const uint64_t b = uni64(bytes[i]);
+    if (b > max_bytes) return false;
+    p = (const uint8_t*)uni64((uint64_t)ptrs[i]);
+    n = (int)b;
+    return true;
+}

@@ -55,6 +55,26 @@ hipError_t lzh_launch_snappy_split(const uint8_t* in, uint64_t n_total, uint64_t
 size_t lzh_snappy_rec_stride(uint64_t chunk_size);
 uint32_t lzh_snappy_frags(uint64_t chunk_size);
 
+// ragged batches (ragged_hip.hip, pack_hip.hip): chunk i = in_bytes[i] bytes at in_ptrs[i] (device arrays), every
+// slot sized for max_bytes (staging: stride; records: lzh_*_rec_stride(max_bytes), then the per-chunk record
+// counts as in the split launchers above); a chunk larger than max_bytes gets csizes[i] = 0
+hipError_t lzh_launch_lz4_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
+                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
+                                 hipStream_t s);
+hipError_t lzh_launch_snappy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                    uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
+                                    hipStream_t s);
+hipError_t lzh_launch_pack_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                  const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
+                                  uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s);
+// fragments per chunk of a ragged snappy batch (at least 1: the launch grid of a batch of empty chunks)
+uint32_t lzh_snappy_ragged_frags(uint64_t max_bytes);
+// block descriptors (32 bytes each, for lzh_launch_decompress) of a ragged batch: absolute output addresses;
+// an out_bytes[i] above max_bytes gives a skipped descriptor and status[i] = -1
+hipError_t lzh_launch_ragged_desc(const uint64_t* offsets, const uint32_t* csizes, void* const* out_ptrs,
+                                  const uint64_t* out_bytes, uint64_t max_bytes, void* desc, int32_t* status,
+                                  uint32_t nchunks, hipStream_t s);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

@@ -945,6 +945,7 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
 
 }  // namespace snv2
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (ragged_hip.hip includes this file for its device functions and kernel bodies alone)
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_compress_v2_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                               uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t chunk0,
@@ -978,6 +979,8 @@ lzh_snappy_compress_v2_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_r
     if (lane == 0) csizes[chunk] = (uint32_t)op;
 }
 
+#endif
+
 // ======================================================================= parse + emit split
 // As for LZ4 (lz4c_hip.hip): the parse kernel (the loop above with kRec, no output marks) leaves
 // 8-byte records; lzh_snappy_emit_kernel (no hash table: high occupancy) writes the varint header
@@ -990,6 +993,7 @@ lzh_snappy_compress_v2_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_r
 // whole chunks at -b256 and above.
 constexpr int kFragRecs = 16384 + 32;
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_parse_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                         uint8_t* recs, uint64_t rec_stride, uint32_t* rec_hdr, uint32_t frags) {
@@ -1000,21 +1004,9 @@ lzh_snappy_parse_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readabl
     const uint64_t off = chunk * chunk_size;
     if (off >= n_total && !(n_total == 0 && chunk == 0)) return;
     const uint32_t n = (uint32_t)min(chunk_size, n_total - off);
-    const rsrc_t rr = make_rsrc(recs + chunk * rec_stride, (uint32_t)rec_stride);
-    uint32_t* hdr = rec_hdr + chunk * frags;       // end record (exclusive) of each fragment
-    int nrec = frags > 1 ? (int)f * kFragRecs : 0;
-    const uint32_t fpos = f << 16;
-    if (fpos < n) {
-        const int fn = (int)min(65536u, n - fpos);
-        const uint64_t readable = min<uint64_t>(in_readable - off - fpos, (uint64_t)fn + 64);
-        Bytes rin, rout;
-        rin.init(in + off + fpos, readable);
-        rout.init(nullptr, 0);
-        snv2::compress_fragment<true>(rin, fn, rout, 0, (LDSA uint16_t*)lds, (LDSA uint32_t*)lds + (1 << 13), nullptr,
-                                      nullptr, rr, nrec, (int)fpos);
-    }
-    if (threadIdx.x == 0) hdr[f] = (uint32_t)nrec;
+#include "snappyc_parse_body.inc"
 }
+#endif
 
 
 
@@ -1272,53 +1264,12 @@ __device__ __forceinline__ void emit_chunk(LDSA uint8_t* rings, LDSA uint32_t* i
     const uint64_t off = chunk * chunk_size;
     if (off >= n_total && !(n_total == 0 && chunk == 0)) return;
     const uint32_t n = (uint32_t)min(chunk_size, n_total - off);
-    LDSA uint8_t* ring = rings + wave * kRingB;
-    LDSA uint32_t* ibuf = ibufs + wave * kSpanDw;
-    Bytes in_b;
-    in_b.init(in + off, min<uint64_t>(in_readable - off, (uint64_t)n + 64));
-    const rsrc_t rr = make_rsrc(recs + chunk * rec_stride, (uint32_t)rec_stride);
-    const uint32_t* hdr = rec_hdr + chunk * frags;
-    const int nf = (int)((n + 65535u) >> 16);
-    const rsrc_t so = make_rsrc(stage + chunk * stride, (uint32_t)stride);
-    int nb = 1;                                    // varint32 uncompressed length (snappy.cc:1047-1050)
-    for (uint32_t v = n; v >= 128; v >>= 7) nb++;
-    if constexpr (!kMulti) {   // one fragment (chunks of at most 64 KiB)
-        OutR<false> R{ring, so, 0};
-        if (lane < nb) R.put(lane, ((n >> (7 * lane)) & 0x7fu) | (lane + 1 < nb ? 0x80u : 0u));
-        const int e = emit_records(R, in_b, rr, 0, (int)uni(hdr[0]), 0, nb, ibuf, lane);
-        R.flush(e, true, lane);
-        if (lane == 0) csizes[chunk] = (uint32_t)e;
-    } else {
-    // sizes of all fragments but the last (the last one's end is the chunk's compressed size)
-    for (int f = wave; f < nf - 1; f += W) {
-        const int r0 = f * kFragRecs, r1 = (int)uni(hdr[f]);
-        const int bytes = frag_bytes(rr, r0, r1, f << 16, lane);
-        if (lane == 0) fsz[f] = (uint32_t)bytes;
-    }
-    if (kMulti) __syncthreads();
-    // the varint goes through fragment 0's ring (an empty chunk: a store of its own)
-    const uint32_t vb = ((n >> (7 * lane)) & 0x7fu) | (lane + 1 < nb ? 0x80u : 0u);
-    if (nf == 0 && wave == 0) {
-        if (lane < nb) st_u8(so, lane, vb);
-        if (lane == 0) csizes[chunk] = (uint32_t)nb;
-    }
-    int base = nb;
-    for (int f = 0; f < nf; f++) {
-        if ((f % W) == wave) {
-            const int r0 = f * kFragRecs, r1 = (int)uni(hdr[f]);
-            OutR<kMulti> R{ring, so, f == 0 ? 0 : base};
-            if (f == 0 && lane < nb) R.put(lane, vb);
-            const int e = emit_records(R, in_b, rr, r0, r1, f << 16, base, ibuf, lane);
-            R.flush(e, true, lane);
-            if (f == nf - 1 && lane == 0) csizes[chunk] = (uint32_t)e;
-        }
-        if (f < nf - 1) base += (int)uni(((volatile LDSA uint32_t*)fsz)[f]);
-    }
-    }
+#include "snappyc_emit_body.inc"
 }
 
 }  // namespace sne
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY
 // -b64 and smaller chunks: a single fragment, one wave
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_emit_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
@@ -1400,3 +1351,4 @@ extern "C" int lzh_debug_snappy_clocks(unsigned long long* host, int reset) {
     return 0;
 }
 #endif
+#endif   // LZH_DEVICE_FUNCTIONS_ONLY
