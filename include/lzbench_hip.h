@@ -174,7 +174,8 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
  * lzh_ragged_max_packed_bytes is the capacity no batch of that total size and chunk count exceeds.
  * Temp: nchunks staging slots, then nchunks sequence-record slots, each sized for max_chunk_bytes (compress);
  * scanned offsets and nchunks 32-byte block descriptors (decompress).  One large chunk therefore makes every
- * slot large: a skewed batch pays nchunks x the largest chunk in temp (size-binned slots would not; not done).
+ * slot large: a skewed batch pays nchunks x the largest chunk in temp.  The compact calls below size every
+ * slot from its own chunk instead.
  * Checks (codec, max_chunk_bytes, null pointers, then temp_bytes below the sizing answer: LZH_ESPACE) come
  * before any device call; the sizing functions are host arithmetic.
  * d_offsets of the decompress call may be NULL (derived from d_csizes into d_temp).  d_status[i]: decoded
@@ -190,6 +191,41 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
                                 const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
                                 size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
                                 size_t temp_bytes, void* hip_stream);
+
+/* Compact compress layout: lzh_compress_ragged_async with every chunk's staging slot and record slot sized
+ * from that chunk's own d_in_bytes[i] (256-aligned) and placed by an exclusive scan on the device, so temp
+ * grows with the batch's total bytes (about 3.1 x total for LZ4, 3.2 x for snappy) plus some 600 bytes and the
+ * record-count header per chunk, not with nchunks x max_chunk_bytes: 4096 chunks of which one has 16 MiB and
+ * the others 4 KiB size to ~100 MiB instead of ~192 GiB.  Codecs, levels, limits, the packed output
+ * (d_csizes, d_offsets, the packed bytes, the raw-store rule) and the order of the checks are those of
+ * lzh_compress_ragged_async; for a batch that keeps the promise below every output byte equals that call's.
+ * The decompress side needs no counterpart (its temp is offsets and descriptors).
+ * total_in_bytes: the caller's host-side upper bound of the sum of d_in_bytes[i] over the chunks that are not
+ * larger than max_chunk_bytes -- the sizes live on the device and nothing is read back, the packed_cap rule.
+ * The sizing function's answer covers every batch of at most nchunks chunks, each of at most max_chunk_bytes,
+ * that sums to at most total_in_bytes, and is non-decreasing in each argument; 0 for other codecs or
+ * max_chunk_bytes over 16 MiB.  Both functions derive a staging region and a record region from the same three
+ * numbers.  On the device a chunk is processed exactly when both of its slots end inside their regions; a
+ * chunk that is not (only in a batch that breaks the promise) is handled as a chunk over max_chunk_bytes:
+ * d_csizes[i] = 0, no packed bytes, no kernel touches a slot for it.  A chunk over max_chunk_bytes takes
+ * slots of 0 bytes.  Every slot is addressed through a buffer descriptor of its own size, so nothing is
+ * written outside d_temp[0 .. temp_bytes) whatever the sizes on the device say. */
+size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes,
+                                              size_t nchunks);
+int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                      size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes, void* d_packed,
+                                      size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp,
+                                      size_t temp_bytes, void* hip_stream);
+/* Host mirror of the compact slot placement for host arrays of sizes (host arithmetic only): stage_off[i] and
+ * rec_off[i] = the offsets of chunk i's slots inside the staging region and the record region, processed[i] =
+ * 1 when the device processes chunk i.  Returns LZH_OK, or LZH_EARG where the async call would. */
+int lzh_debug_ragged_compact_slots(int codec, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                   size_t total_in_bytes, uint64_t* stage_off, uint64_t* rec_off, uint8_t* processed);
+/* Debug only, for tests of the placement (no caller needs it; it may change with the temp layout): the two
+ * regions both functions derive, as byte ranges of d_temp: out[0], out[1] = offset and size of the
+ * staging region, out[2], out[3] = of the record region.  Host arithmetic only; LZH_EARG as above. */
+int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                     uint64_t* out);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

@@ -99,6 +99,10 @@ SIGNATURES = {
     "lzh_ragged_max_packed_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
     "lzh_compress_ragged_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_decompress_ragged_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
+    "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    "lzh_debug_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
     "lzh_compress_kernel_only": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_kernel_stage": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
@@ -368,14 +372,19 @@ class RaggedCodec:
     """Device-resident codec over ragged batches (include/lzbench_hip.h 3b): chunk i of a batch is
     sizes[i] bytes at offsets[i] of a flat uint8 CUDA tensor, any alignment, in any order.
 
-    Buffers are sized once for max_chunks chunks of up to max_chunk_bytes (staging is per chunk at
-    the largest size: a skewed batch pays for its largest chunk max_chunks times); max_total_bytes
-    bounds a batch's total input (default max_chunks * max_chunk_bytes) and sizes `packed`.
+    Buffers are sized once for max_chunks chunks of up to max_chunk_bytes; max_total_bytes bounds a
+    batch's total input (default max_chunks * max_chunk_bytes) and sizes `packed`.  The compress temp
+    has a staging slot and a sequence-record slot per chunk.  compact=False sizes every slot for
+    max_chunk_bytes: a skewed batch pays for its largest chunk max_chunks times.  compact=True sizes
+    each slot from its own chunk (lzh_compress_ragged_compact_async): the temp grows with
+    max_total_bytes (about 3.2 x) plus some 600 bytes per chunk, the output is the same, and a batch
+    must keep its total within max_total_bytes (checked on the host by compress(); compress_arrays()
+    leaves a chunk whose slots do not fit uncompressed with csizes[i] = 0).
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
     def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
-                 max_total_bytes: Optional[int] = None):
+                 max_total_bytes: Optional[int] = None, compact: bool = False):
         import torch
         self.torch = torch
         self.codec = CODECS[codec]
@@ -383,7 +392,11 @@ class RaggedCodec:
         self.max_chunk_bytes, self.max_chunks = max_chunk_bytes, max_chunks
         self.max_total = max_chunks * max_chunk_bytes if max_total_bytes is None else max_total_bytes
         L = lib()
-        ct = L.lzh_ragged_compress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
+        self.compact = compact
+        if compact:
+            ct = L.lzh_ragged_compact_compress_temp_bytes(self.codec, self.max_total, max_chunk_bytes, max_chunks)
+        else:
+            ct = L.lzh_ragged_compress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
         dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
         if ct == 0 or dt == 0:
             raise ValueError(f"ragged batches: codec {codec} / chunks of {max_chunk_bytes} bytes are not supported")
@@ -425,12 +438,16 @@ class RaggedCodec:
         copy, so the call can be captured in a graph."""
         self._in = d   # (kept alive until the next call: the kernels read it asynchronously)
         self.k = k
-        rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
-                                             self.max_chunk_bytes, self.packed.data_ptr(), self.packed.numel(),
-                                             self.csizes.data_ptr(), self.offsets.data_ptr(), self.ctemp.data_ptr(),
-                                             self.ctemp.numel(), self._stream())
+        out = (self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
+               self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
+        if self.compact:
+            rc = lib().lzh_compress_ragged_compact_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
+                                                         self.max_chunk_bytes, self.max_total, *out)
+        else:
+            rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
+                                                 self.max_chunk_bytes, *out)
         if rc:
-            raise RuntimeError(f"lzh_compress_ragged_async failed ({rc})")
+            raise RuntimeError(f"lzh_compress_ragged{'_compact' if self.compact else ''}_async failed ({rc})")
 
     def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:
         """Decode chunk i to out_buf[out_offsets[i] : out_offsets[i] + out_sizes[i]]; self.status[i] = its

@@ -23,6 +23,9 @@
 
 #include "../../include/lzbench_hip.h"
 #include "launch.h"
+#include "ragged_slots.h"
+
+static_assert(kLzhSlotLz4 == LZH_CODEC_LZ4 && kLzhSlotSnappy == LZH_CODEC_SNAPPY, "ragged_slots.h: codec numbers");
 
 // rocprof-visible ranges around each stage's launches (rocprofv3 --marker-trace); a range covers
 // the enqueue of the stage on the host, the kernels themselves show in --kernel-trace
@@ -442,6 +445,99 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
     // (the block decoder adds the descriptor's destination, the chunk's address, to a null output base)
     LZH_CHECK(lzh_launch_decompress(codec, (const uint8_t*)d_packed, packed_readable, nullptr, nullptr, 0, 0, nullptr,
                                     d_status, (uint32_t)nchunks, s, desc));
+    return LZH_OK;
+}
+
+// ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h) ----
+// temp: staging region | record region, then the per-chunk record counts (sized for max_chunk_bytes as
+// above) | staging-slot sizes | record-slot sizes (u32 each) | staging-slot offsets | record-slot offsets
+// (nchunks + 1 u64 each, scanned on the device).  One function lays it out for the sizing call, the async
+// call and the host mirror.
+struct CompactTemp {
+    LzhCompactRegions reg;
+    size_t recs, hdr, stage_sz, rec_sz, stage_off, rec_off, total;
+};
+static CompactTemp compact_temp(int codec, size_t total_in, size_t max_bytes, size_t nchunks) {
+    CompactTemp t;
+    t.reg = lzh_compact_regions(codec, total_in, max_bytes, nchunks);
+    t.recs = t.reg.stage + 256;
+    t.hdr = t.recs + t.reg.recs;
+    const size_t hdr_bytes = codec == LZH_CODEC_LZ4 ? nchunks * 8 : nchunks * 4 * lzh_snappy_ragged_frags(max_bytes);
+    t.stage_sz = t.hdr + align_up(hdr_bytes, 256) + 256;
+    t.rec_sz = t.stage_sz + align_up(nchunks * 4, 256);
+    t.stage_off = t.rec_sz + align_up(nchunks * 4, 256);
+    t.rec_off = t.stage_off + align_up((nchunks + 1) * 8, 256);
+    t.total = t.rec_off + align_up((nchunks + 1) * 8, 256) + 256;
+    return t;
+}
+
+size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
+    return compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks).total;
+}
+
+int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                     uint64_t* out) {
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax || !out) return LZH_EARG;
+    const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
+    out[0] = 0;
+    out[1] = t.reg.stage;
+    out[2] = t.recs;
+    out[3] = t.reg.recs;
+    return LZH_OK;
+}
+
+int lzh_debug_ragged_compact_slots(int codec, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                   size_t total_in_bytes, uint64_t* stage_off, uint64_t* rec_off, uint8_t* processed) {
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!sizes || !stage_off || !rec_off || !processed) return LZH_EARG;
+    const LzhCompactRegions reg = lzh_compact_regions(codec, total_in_bytes, max_chunk_bytes, nchunks);
+    uint64_t so = 0, ro = 0;
+    for (size_t i = 0; i < nchunks; i++) {   // lzh_compact_slots_kernel, the two scans, compact_span
+        const bool over = sizes[i] > max_chunk_bytes;
+        const uint64_t ss = over ? 0 : lzh_slot_stage_bytes(codec, sizes[i]);
+        const uint64_t rs = over ? 0 : lzh_slot_rec_bytes(codec, sizes[i], max_chunk_bytes > 65536);
+        stage_off[i] = so;
+        rec_off[i] = ro;
+        processed[i] = !over && so + ss <= reg.stage && ro + rs <= reg.recs;
+        so += ss;
+        ro += rs;
+    }
+    return LZH_OK;
+}
+
+int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                      size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes, void* d_packed,
+                                      size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp,
+                                      size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
+    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
+    const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
+    if (temp_bytes < t.total) return LZH_ESPACE;
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    uint8_t* stage = base;
+    uint8_t* recs = base + t.recs;
+    uint32_t* hdr = (uint32_t*)(base + t.hdr);
+    const LzhCompactLayout L = {(uint32_t*)(base + t.stage_sz), (uint32_t*)(base + t.rec_sz),
+                                (uint64_t*)(base + t.stage_off), (uint64_t*)(base + t.rec_off), t.reg.stage, t.reg.recs};
+    {
+        Range range("lzh:compress_kernel");
+        LZH_CHECK(lzh_launch_compact_slots(codec, d_in_bytes, max_chunk_bytes, L, k, s));
+        if (codec == LZH_CODEC_LZ4)
+            LZH_CHECK(lzh_launch_lz4_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level, stage, d_csizes,
+                                             k, recs, hdr, L, s));
+        else
+            LZH_CHECK(lzh_launch_snappy_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, d_csizes, k, recs, hdr, L, s));
+    }
+    Range range("lzh:scan_pack");
+    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
+    LZH_CHECK(lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, d_csizes, d_offsets,
+                                      (uint8_t*)d_packed, packed_cap, k, L, s));
     return LZH_OK;
 }
 

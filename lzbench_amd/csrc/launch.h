@@ -75,6 +75,33 @@ hipError_t lzh_launch_ragged_desc(const uint64_t* offsets, const uint32_t* csize
                                   const uint64_t* out_bytes, uint64_t max_bytes, void* desc, int32_t* status,
                                   uint32_t nchunks, hipStream_t s);
 
+// the compact layout of a ragged compression (ragged_compact_hip.hip, ragged_slots.h): chunk i's staging slot is
+// stage_sz[i] bytes at stage_off[i] of a staging region of stage_cap bytes, its record slot rec_sz[i] bytes at
+// rec_off[i] of a record region of rec_cap bytes (device arrays: nchunks u32, nchunks + 1 u64).
+// lzh_launch_compact_slots fills the four arrays (the slot-size kernel, then lzh_launch_scan twice); the other
+// launchers are the ragged ones above with the slots looked up there; hdr: the per-chunk record counts.  A chunk
+// larger than max_bytes, or one with a slot that ends past its region, gets csizes[i] = 0.
+// (the arrays are written by lzh_launch_compact_slots alone; every other kernel takes the struct as const)
+struct LzhCompactLayout {
+    uint32_t* stage_sz;
+    uint32_t* rec_sz;
+    uint64_t* stage_off;
+    uint64_t* rec_off;
+    uint64_t stage_cap, rec_cap;
+};
+hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,
+                                    uint32_t nchunks, hipStream_t s);
+hipError_t lzh_launch_lz4_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
+                                  uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
+                                  const LzhCompactLayout& L, hipStream_t s);
+hipError_t lzh_launch_snappy_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                     uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
+                                     const LzhCompactLayout& L, hipStream_t s);
+hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                   const uint8_t* stage, const uint32_t* csizes, const uint64_t* offsets,
+                                   uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, const LzhCompactLayout& L,
+                                   hipStream_t s);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

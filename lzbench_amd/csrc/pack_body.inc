@@ -9,7 +9,7 @@
     if (doff + cs > packed_cap) return;   // caller sized packed from offsets[nchunks]
     const bool raw = cs == part;
     const uint8_t* sp = raw ? in + ioff : stage + c * stride;
-    const uint64_t sread = raw ? min<uint64_t>(in_readable - ioff, (uint64_t)part + 8) : stride;
+    const uint64_t sread = raw ? min<uint64_t>(in_readable - ioff, (uint64_t)part + 8) : (uint64_t)stride;
     Bytes src, dst;
     src.init(sp, sread);
     dst.init(packed + doff, cs);
