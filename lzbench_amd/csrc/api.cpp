@@ -24,6 +24,7 @@
 #include "../../include/lzbench_hip.h"
 #include "launch.h"
 #include "ragged_slots.h"
+#include "temp_layout.h"
 
 static_assert(kLzhSlotLz4 == LZH_CODEC_LZ4 && kLzhSlotSnappy == LZH_CODEC_SNAPPY, "ragged_slots.h: codec numbers");
 
@@ -44,12 +45,6 @@ extern "C" size_t lzb_datagen(int kind, uint64_t seed, uint8_t* buf, size_t n);
             return LZH_EHIP;                                                          \
         }                                                                             \
     } while (0)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// LZ4 chunks up to this size compress in two kernels (parse -> 8-byte sequence records -> emit);
-// larger ones (24-bit record fields) in the single kernel that assembles the block itself
-static const size_t kLz4SplitMax = (size_t)16 << 20;   // LZ4 / snappy parse + emit split up to this chunk size
 
 extern "C" {
 
@@ -83,12 +78,7 @@ size_t lzh_max_packed_bytes(int codec, size_t n, size_t chunk_size) {
     return n + k * (codec_bound(codec, chunk_size) - chunk_size + 8) + 64;
 }
 
-// Framed layouts: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes
-struct FrameGeo {
-    size_t F, bs, nframes, nblocks;
-    uint32_t bpf;
-};
-
+// Framed layouts: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes (FrameGeo, temp_layout.h)
 static size_t frame_block_bytes(int codec, int level) {
     if (codec == LZH_CODEC_LZ4F) { const int id = level & 7; return (size_t)1 << (8 + 2 * (id ? id : 4)); }
     return (size_t)32768 << level;
@@ -105,36 +95,7 @@ extern "C" int lzh_level_supported(int codec, int level, size_t chunk_size) {
     return codec >= LZH_CODEC_LZ4 && codec <= LZH_CODEC_MEMCPY ? 1 : 0;
 }
 
-
-static FrameGeo frame_geo(size_t B, size_t n, size_t F) {
-    FrameGeo g;
-    g.F = F;
-    g.bs = std::min(F, B);
-    g.bpf = (uint32_t)((F + g.bs - 1) / g.bs);
-    g.nframes = lzh_num_chunks(n, F);
-    if (n == 0) {
-        g.nblocks = 0;
-    } else {
-        const size_t last = n - (g.nframes - 1) * F;
-        g.nblocks = (g.nframes - 1) * g.bpf + (last + g.bs - 1) / g.bs;
-    }
-    return g;
-}
-
-// temp of a framed compression: staging slots | LZ4 sequence records (+ 8 B per block) | block
-// sizes | block offsets inside their frame
-struct FrameTemp { size_t stride, stage, recs, bcs, rel, total; };
-static FrameTemp frame_temp(const FrameGeo& g) {
-    FrameTemp t;
-    t.stride = lzh_stage_stride(LZH_CODEC_LZ4, g.bs);
-    t.stage = 0;
-    t.recs = align_up(g.nblocks * t.stride, 256) + 256;
-    t.bcs = t.recs + g.nblocks * lzh_lz4_rec_stride(g.bs) + align_up(g.nblocks * 8, 256) + 256;
-    t.rel = t.bcs + align_up(g.nblocks * 4, 256) + 256;
-    t.total = t.rel + align_up(g.nblocks * 4, 256) + 256;
-    return t;
-}
-
+// (the sizing call does not know the level: the largest temp of the block sizes a level can select)
 static size_t frame_temp_worst(int codec, size_t n, size_t F) {
     size_t t = 0;
     for (int l = 0; l < 6; l++) {
@@ -144,40 +105,13 @@ static size_t frame_temp_worst(int codec, size_t n, size_t F) {
     return t;
 }
 
-// decode side: maxbpf descriptor slots per frame (blocks of 64 KiB / 32 KiB at the least)
-static uint32_t frame_maxbpf(int codec, size_t F) {
-    const size_t bmin = codec == LZH_CODEC_LZ4F ? 65536 : 32768;
-    return (uint32_t)std::max<size_t>(1, (F + bmin - 1) / bmin);
-}
-
 size_t lzh_compress_temp_bytes(int codec, size_t n, size_t chunk_size) {
-    size_t k = lzh_num_chunks(n, chunk_size);
     if (codec == LZH_CODEC_MEMCPY) return 256;
     if (is_frame(codec)) return frame_temp_worst(codec, n, chunk_size) + 256;
-    size_t t = align_up(k * lzh_stage_stride(codec, chunk_size), 256) + 256;
-    if (codec == LZH_CODEC_LZ4 && chunk_size <= kLz4SplitMax)     // sequence records of the parse kernel
-        t += k * lzh_lz4_rec_stride(chunk_size) + align_up(k * 8, 256) + 256;
-    if (codec == LZH_CODEC_SNAPPY && chunk_size <= kLz4SplitMax)
-        t += k * lzh_snappy_rec_stride(chunk_size) + align_up(k * 4 * lzh_snappy_frags(chunk_size), 256) + 256;
-    if (codec == LZH_CODEC_ZSTD) {   // per-frame scratch of the two zstd kernels (zstdc_hip.hip), worst level
-        size_t fs = 0;
-        for (int lv : {1, 2, -1, -2}) fs = std::max(fs, lzh_zstd_scratch_stride(chunk_size, lv));
-        t += k * fs + 256;
-    }
-    return t;
+    return chunk_temp(codec, lzh_num_chunks(n, chunk_size), chunk_size).total;
 }
 
-size_t lzh_decompress_temp_bytes(int codec, size_t n, size_t chunk_size) {
-    const size_t k = lzh_num_chunks(n, chunk_size);
-    size_t t = align_up((k + 1) * sizeof(uint64_t), 256) + 256;
-    if (is_frame(codec)) {   // block descriptors, block statuses, frame statuses
-        const size_t nd = k * frame_maxbpf(codec, chunk_size);
-        t += align_up(nd * 32, 256) + align_up(nd * 4, 256) + align_up(k * 4, 256) + 256;
-    }
-    if (codec == LZH_CODEC_ZSTD) t += lzh_zstd_decode_temp(n, chunk_size);   // the split decoder (decode_hip.hip)
-    if (codec == LZH_CODEC_SNAPPY) t += lzh_snappy_split_temp(n, chunk_size); // fragment-parallel decode
-    return t;
-}
+size_t lzh_decompress_temp_bytes(int codec, size_t n, size_t chunk_size) { return decode_temp(codec, n, chunk_size).total; }
 
 int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* d_in, size_t n, size_t in_readable,
                               size_t chunk_size, void* d_stage, uint32_t* d_csizes, void* hip_stream) {
@@ -185,32 +119,33 @@ int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* 
     if (!chunk_size || !d_stage || !d_csizes || (n && !d_in)) return LZH_EARG;
     const size_t k = lzh_num_chunks(n, chunk_size);
     if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
-    const size_t stride = lzh_stage_stride(codec, chunk_size);
+    uint8_t* base = (uint8_t*)d_stage;
     Range range("lzh:compress_kernel");
     if (codec == LZH_CODEC_LZ4) {
-        if (chunk_size <= kLz4SplitMax) {
-            uint8_t* recs = (uint8_t*)d_stage + align_up(k * stride, 256) + 256;
+        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
+        if (t.split) {
             LZH_CHECK(lzh_launch_lz4_split((const uint8_t*)d_in, n, in_readable, chunk_size, level < 1 ? 1 : level,
-                                           (uint8_t*)d_stage, stride, d_csizes, (uint32_t)k, recs, stage_mask, s));
+                                           base + t.stage, t.stride, d_csizes, (uint32_t)k, base + t.recs, t.rec_stride,
+                                           (uint32_t*)(base + t.hdr), stage_mask, s));
         } else if (stage_mask & 1) {
             LZH_CHECK(lzh_launch_lz4_compress_v2((const uint8_t*)d_in, n, in_readable, chunk_size, level < 1 ? 1 : level,
-                                                 (uint8_t*)d_stage, stride, d_csizes, (uint32_t)k, s));
+                                                 base + t.stage, t.stride, d_csizes, (uint32_t)k, s));
         }
     } else if (codec == LZH_CODEC_SNAPPY) {
-        if (chunk_size <= kLz4SplitMax) {
-            uint8_t* recs = (uint8_t*)d_stage + align_up(k * stride, 256) + 256;
-            LZH_CHECK(lzh_launch_snappy_split((const uint8_t*)d_in, n, in_readable, chunk_size, (uint8_t*)d_stage,
-                                              stride, d_csizes, (uint32_t)k, recs, stage_mask, s));
+        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
+        if (t.split) {
+            LZH_CHECK(lzh_launch_snappy_split((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage, t.stride,
+                                              d_csizes, (uint32_t)k, base + t.recs, t.rec_stride,
+                                              (uint32_t*)(base + t.hdr), stage_mask, s));
         } else if (stage_mask & 1) {
-            LZH_CHECK(lzh_launch_snappy_compress_v2((const uint8_t*)d_in, n, in_readable, chunk_size, (uint8_t*)d_stage,
-                                                    stride, d_csizes, (uint32_t)k, s));
+            LZH_CHECK(lzh_launch_snappy_compress_v2((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage,
+                                                    t.stride, d_csizes, (uint32_t)k, s));
         }
     } else if (is_frame(codec)) {
         // (d_stage = the whole compression temp of a framed layout; d_csizes = frame sizes)
         if (!frame_level_ok(codec, level)) return LZH_EARG;
         const FrameGeo g = frame_geo(frame_block_bytes(codec, level), n, chunk_size);
         const FrameTemp t = frame_temp(g);
-        uint8_t* base = (uint8_t*)d_stage;
         uint32_t* bcs = (uint32_t*)(base + t.bcs);
         const int acc = codec == LZH_CODEC_LZ4F ? std::max(1, (level >> 8) & 0xff) : 1;
         if (codec == LZH_CODEC_LZ4F && (level & LZH_LZ4F_LINKED)) {
@@ -222,17 +157,18 @@ int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* 
                                                  (uint32_t)g.nframes, s));
         } else {
             LZH_CHECK(lzh_launch_lz4_split((const uint8_t*)d_in, n, in_readable, g.bs, acc, base + t.stage, t.stride, bcs,
-                                           (uint32_t)g.nblocks, base + t.recs, stage_mask, s, g.F, g.bpf));
+                                           (uint32_t)g.nblocks, base + t.recs, t.rec_stride, (uint32_t*)(base + t.hdr),
+                                           stage_mask, s, g.F, g.bpf));
         }
         if (stage_mask & 2)
             LZH_CHECK(lzh_launch_frame_sizes(codec, level, n, g.F, g.bs, g.bpf, bcs, (uint32_t*)(base + t.rel), d_csizes,
                                              (uint32_t)g.nframes, s));
     } else if (codec == LZH_CODEC_ZSTD) {
         if (!lzh_zstd_level_ok(level, chunk_size)) return LZH_EARG;
-        uint8_t* scratch = (uint8_t*)d_stage + align_up(k * stride, 256) + 256;
+        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
         if (stage_mask & 1)
-            LZH_CHECK(lzh_launch_zstd_compress((const uint8_t*)d_in, n, in_readable, chunk_size, level,
-                                               (uint8_t*)d_stage, stride, d_csizes, (uint32_t)k, scratch, s));
+            LZH_CHECK(lzh_launch_zstd_compress((const uint8_t*)d_in, n, in_readable, chunk_size, level, base + t.stage,
+                                               t.stride, d_csizes, (uint32_t)k, base + t.recs, s));
     } else {
         return LZH_EARG;
     }
@@ -300,10 +236,10 @@ int lzh_compress_finish_async(int codec, const void* d_in, size_t n, size_t in_r
     // the sizes are only known on the device: the worst case must fit (no silent truncation)
     if (packed_cap < lzh_max_packed_bytes(codec, n, chunk_size)) return LZH_ESPACE;
     const size_t k = lzh_num_chunks(n, chunk_size);
-    const size_t stride = lzh_stage_stride(codec, chunk_size);
+    const ChunkTemp t = chunk_temp(codec, k, chunk_size);
     Range range("lzh:scan_pack");
     LZH_CHECK(lzh_launch_scan(d_csizes, k, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack((const uint8_t*)d_in, n, in_readable, chunk_size, (const uint8_t*)d_stage, stride,
+    LZH_CHECK(lzh_launch_pack((const uint8_t*)d_in, n, in_readable, chunk_size, (const uint8_t*)d_stage + t.stage, t.stride,
                               d_csizes, d_offsets, (uint8_t*)d_packed, packed_cap, (uint32_t)k, s));
     return LZH_OK;
 }
@@ -319,27 +255,24 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
     if (n == 0) return LZH_OK;
     Range range("lzh:decompress");
     const uint64_t* offs = d_offsets;
-    const size_t scan_bytes = align_up((k + 1) * sizeof(uint64_t), 256);
-    if (is_frame(codec) && (!d_temp || temp_bytes < lzh_decompress_temp_bytes(codec, n, chunk_size))) return LZH_ESPACE;
-    if (!offs && (!d_temp || temp_bytes < scan_bytes + 256)) return LZH_ESPACE;
-    // zstd: the split decoder's per-frame layout lives in temp after the offsets; without room for it
-    // (or for chunks below lzh_zstd_split_min) every frame takes the one-wave decoder
-    uint8_t* zt = nullptr;
-    if (codec == LZH_CODEC_ZSTD && d_temp && temp_bytes >= lzh_decompress_temp_bytes(codec, n, chunk_size) &&
-        lzh_zstd_decode_temp(n, chunk_size) > 0)
-        zt = (uint8_t*)d_temp + scan_bytes;
+    const DecodeTemp t = decode_temp(codec, n, chunk_size);
+    uint8_t* base = (uint8_t*)d_temp;
+    if (is_frame(codec) && (!d_temp || temp_bytes < t.total)) return LZH_ESPACE;
+    if (!offs && (!d_temp || temp_bytes < t.need_scan)) return LZH_ESPACE;
+    // zstd, snappy chunks of several 64 KiB fragments: the split decoder's layout lives in temp after the offsets;
+    // without room for it (or for chunks it does not take) every chunk is decoded whole by one wave
+    uint8_t* split = d_temp && t.need_split && temp_bytes >= t.need_split ? base + t.split : nullptr;
     if (!offs) {
-        LZH_CHECK(lzh_launch_scan(d_csizes, k, (uint64_t*)d_temp, nullptr, s));
-        offs = (const uint64_t*)d_temp;
+        LZH_CHECK(lzh_launch_scan(d_csizes, k, (uint64_t*)(base + t.scan), nullptr, s));
+        offs = (const uint64_t*)(base + t.scan);
     }
     if (is_frame(codec)) {   // frame headers -> block descriptors -> blocks -> frame checks
         if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
         const uint32_t mb = frame_maxbpf(codec, chunk_size);
         const size_t nd = k * mb;
-        uint8_t* t = (uint8_t*)d_temp + align_up((k + 1) * sizeof(uint64_t), 256);
-        void* desc = t;
-        int32_t* bstat = (int32_t*)(t + align_up(nd * 32, 256));
-        int32_t* fstat = (int32_t*)(t + align_up(nd * 32, 256) + align_up(nd * 4, 256));
+        void* desc = base + t.desc;
+        int32_t* bstat = (int32_t*)(base + t.bstat);
+        int32_t* fstat = (int32_t*)(base + t.fstat);
         if (nd > 0xffffffffu) return LZH_EARG;
         LZH_CHECK(lzh_launch_frame_parse(codec, (const uint8_t*)d_packed, packed_readable, offs, d_csizes, n, chunk_size,
                                          mb, desc, fstat, (uint32_t)k, s));
@@ -349,16 +282,12 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
                                           bstat, fstat, (const uint8_t*)d_out, d_status, (uint32_t)k, s));
         return LZH_OK;
     }
-    // snappy chunks of several 64 KiB fragments decode a fragment per wave when temp has room for the split
-    // (else, or for chunks of one fragment, whole)
-    const size_t sst = codec == LZH_CODEC_SNAPPY ? lzh_snappy_split_temp(n, chunk_size) : 0;
     if (codec == LZH_CODEC_ZSTD)
         LZH_CHECK(lzh_launch_zstd_decompress((const uint8_t*)d_packed, packed_readable, offs, d_csizes, n, chunk_size,
-                                             (uint8_t*)d_out, d_status, (uint32_t)k, zt, s));
-    else if (sst && d_temp && temp_bytes >= scan_bytes + sst)
+                                             (uint8_t*)d_out, d_status, (uint32_t)k, split, s));
+    else if (split)   // (snappy: a fragment per wave)
         LZH_CHECK(lzh_launch_snappy_split_decompress((const uint8_t*)d_packed, packed_readable, offs, d_csizes, n,
-                                                     chunk_size, (uint8_t*)d_out, d_status, (uint32_t)k,
-                                                     (uint8_t*)d_temp + scan_bytes, s));
+                                                     chunk_size, (uint8_t*)d_out, d_status, (uint32_t)k, split, s));
     else
         LZH_CHECK(lzh_launch_decompress(codec, (const uint8_t*)d_packed, packed_readable, offs, d_csizes, n,
                                         chunk_size, (uint8_t*)d_out, d_status, (uint32_t)k, s));
@@ -366,25 +295,18 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
 }
 
 // ---- 3b. ragged batches: chunk i = d_in_bytes[i] bytes at d_in_ptrs[i] (device arrays) ----
-// compress temp: nchunks staging slots | sequence records (nchunks record slots, then the per-chunk record
-// counts), all sized for max_chunk_bytes.  decompress temp: scanned offsets | nchunks block descriptors.
+// compress temp: chunk_temp of nchunks slots sized for max_chunk_bytes; decompress temp: ragged_decode_temp
 
-static bool ragged_codec(int codec) { return codec == LZH_CODEC_LZ4 || codec == LZH_CODEC_SNAPPY; }
+static bool ragged_ok(int codec, size_t max_chunk_bytes) {
+    return (codec == LZH_CODEC_LZ4 || codec == LZH_CODEC_SNAPPY) && max_chunk_bytes <= kLz4SplitMax;
+}
 
 size_t lzh_ragged_compress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks) {
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
-    size_t t = align_up(nchunks * lzh_stage_stride(codec, max_chunk_bytes), 256) + 256;
-    if (codec == LZH_CODEC_LZ4)
-        t += nchunks * lzh_lz4_rec_stride(max_chunk_bytes) + align_up(nchunks * 8, 256) + 256;
-    else
-        t += nchunks * lzh_snappy_rec_stride(max_chunk_bytes) +
-             align_up(nchunks * 4 * lzh_snappy_ragged_frags(max_chunk_bytes), 256) + 256;
-    return t;
+    return ragged_ok(codec, max_chunk_bytes) ? chunk_temp(codec, nchunks, max_chunk_bytes).total : 0;
 }
 
 size_t lzh_ragged_decompress_temp_bytes(int codec, size_t max_chunk_bytes, size_t nchunks) {
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
-    return align_up((nchunks + 1) * sizeof(uint64_t), 256) + 256 + align_up(nchunks * 32, 256) + 256;
+    return ragged_ok(codec, max_chunk_bytes) ? ragged_decode_temp(nchunks).total : 0;
 }
 
 size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchunks) {
@@ -394,27 +316,39 @@ size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchu
     return total_in_bytes + var + nchunks * (codec_bound(codec, 0) + 8) + 64;
 }
 
+// the argument checks of the two ragged compress calls, in their order: an error, 1 for an empty batch (nothing to
+// do: LZH_OK), 0 to go on.  (The grid limit comes before the caller's temp check.)
+static int ragged_compress_args(int codec, size_t nchunks, size_t max_chunk_bytes, bool pointers) {
+    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
+    if (nchunks == 0) return 1;
+    if (!pointers) return LZH_EARG;
+    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
+    return 0;
+}
+
 int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
                               size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
                               uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
                               void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
-    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
-    if (temp_bytes < lzh_ragged_compress_temp_bytes(codec, max_chunk_bytes, nchunks)) return LZH_ESPACE;
+    const bool ptrs = d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp;
+    if (const int rc = ragged_compress_args(codec, nchunks, max_chunk_bytes, ptrs)) return rc < 0 ? rc : LZH_OK;
+    const ChunkTemp t = chunk_temp(codec, nchunks, max_chunk_bytes);
+    if (temp_bytes < t.total) return LZH_ESPACE;
     const uint32_t k = (uint32_t)nchunks;
-    const size_t stride = lzh_stage_stride(codec, max_chunk_bytes);
-    uint8_t* stage = (uint8_t*)d_temp;
-    uint8_t* recs = stage + align_up(nchunks * stride, 256) + 256;
+    const size_t stride = t.stride;
+    uint8_t* base = (uint8_t*)d_temp;
+    uint8_t* stage = base + t.stage;
+    uint8_t* recs = base + t.recs;
+    uint32_t* hdr = (uint32_t*)(base + t.hdr);
     {
         Range range("lzh:compress_kernel");
         if (codec == LZH_CODEC_LZ4)
             LZH_CHECK(lzh_launch_lz4_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level, stage, stride,
-                                            d_csizes, k, recs, s));
+                                            d_csizes, k, recs, t.rec_stride, hdr, s));
         else
-            LZH_CHECK(lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, k, recs, s));
+            LZH_CHECK(lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, k, recs,
+                                               t.rec_stride, hdr, s));
     }
     Range range("lzh:scan_pack");
     LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
@@ -428,18 +362,19 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
                                 size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
                                 size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
     if (nchunks == 0) return LZH_OK;
     if (!d_packed || !d_csizes || !d_out_ptrs || !d_out_bytes || !d_status || !d_temp) return LZH_EARG;
     if (nchunks > 0x7fffffffu) return LZH_EARG;
-    if (temp_bytes < lzh_ragged_decompress_temp_bytes(codec, max_chunk_bytes, nchunks)) return LZH_ESPACE;
+    const DecodeTemp t = ragged_decode_temp(nchunks);
+    if (temp_bytes < t.total) return LZH_ESPACE;
     Range range("lzh:decompress");
     const uint64_t* offs = d_offsets;
     if (!offs) {
-        LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)d_temp, nullptr, s));
-        offs = (const uint64_t*)d_temp;
+        LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)((uint8_t*)d_temp + t.scan), nullptr, s));
+        offs = (const uint64_t*)((uint8_t*)d_temp + t.scan);
     }
-    void* desc = (uint8_t*)d_temp + align_up((nchunks + 1) * sizeof(uint64_t), 256) + 256;
+    void* desc = (uint8_t*)d_temp + t.desc;
     LZH_CHECK(lzh_launch_ragged_desc(offs, d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes, desc, d_status,
                                      (uint32_t)nchunks, s));
     // (the block decoder adds the descriptor's destination, the chunk's address, to a null output base)
@@ -448,37 +383,16 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
     return LZH_OK;
 }
 
-// ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h) ----
-// temp: staging region | record region, then the per-chunk record counts (sized for max_chunk_bytes as
-// above) | staging-slot sizes | record-slot sizes (u32 each) | staging-slot offsets | record-slot offsets
-// (nchunks + 1 u64 each, scanned on the device).  One function lays it out for the sizing call, the async
-// call and the host mirror.
-struct CompactTemp {
-    LzhCompactRegions reg;
-    size_t recs, hdr, stage_sz, rec_sz, stage_off, rec_off, total;
-};
-static CompactTemp compact_temp(int codec, size_t total_in, size_t max_bytes, size_t nchunks) {
-    CompactTemp t;
-    t.reg = lzh_compact_regions(codec, total_in, max_bytes, nchunks);
-    t.recs = t.reg.stage + 256;
-    t.hdr = t.recs + t.reg.recs;
-    const size_t hdr_bytes = codec == LZH_CODEC_LZ4 ? nchunks * 8 : nchunks * 4 * lzh_snappy_ragged_frags(max_bytes);
-    t.stage_sz = t.hdr + align_up(hdr_bytes, 256) + 256;
-    t.rec_sz = t.stage_sz + align_up(nchunks * 4, 256);
-    t.stage_off = t.rec_sz + align_up(nchunks * 4, 256);
-    t.rec_off = t.stage_off + align_up((nchunks + 1) * 8, 256);
-    t.total = t.rec_off + align_up((nchunks + 1) * 8, 256) + 256;
-    return t;
-}
-
+// ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h); compact_temp
+// lays the temp out for the sizing call, the async call and the host mirror ----
 size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks) {
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return 0;
+    if (!ragged_ok(codec, max_chunk_bytes)) return 0;
     return compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks).total;
 }
 
 int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                      uint64_t* out) {
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax || !out) return LZH_EARG;
+    if (!ragged_ok(codec, max_chunk_bytes) || !out) return LZH_EARG;
     const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
     out[0] = 0;
     out[1] = t.reg.stage;
@@ -489,7 +403,7 @@ int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t ma
 
 int lzh_debug_ragged_compact_slots(int codec, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
                                    size_t total_in_bytes, uint64_t* stage_off, uint64_t* rec_off, uint8_t* processed) {
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
     if (nchunks == 0) return LZH_OK;
     if (!sizes || !stage_off || !rec_off || !processed) return LZH_EARG;
     const LzhCompactRegions reg = lzh_compact_regions(codec, total_in_bytes, max_chunk_bytes, nchunks);
@@ -512,15 +426,13 @@ int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d
                                       size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp,
                                       size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!ragged_codec(codec) || max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
-    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
+    const bool ptrs = d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp;
+    if (const int rc = ragged_compress_args(codec, nchunks, max_chunk_bytes, ptrs)) return rc < 0 ? rc : LZH_OK;
     const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
     if (temp_bytes < t.total) return LZH_ESPACE;
     const uint32_t k = (uint32_t)nchunks;
     uint8_t* base = (uint8_t*)d_temp;
-    uint8_t* stage = base;
+    uint8_t* stage = base + t.stage;
     uint8_t* recs = base + t.recs;
     uint32_t* hdr = (uint32_t*)(base + t.hdr);
     const LzhCompactLayout L = {(uint32_t*)(base + t.stage_sz), (uint32_t*)(base + t.rec_sz),

@@ -45,25 +45,38 @@ int lzh_zstd_level_ok(int level, size_t chunk_size);
 hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,
                                   uint32_t bpf, int acc, uint8_t* stage, uint64_t stride, uint32_t* bcs, uint32_t* snap,
                                   uint32_t nframes, hipStream_t s);
+// recs / rec_stride / hdr (here and in the snappy and ragged launchers below): the record slots and the per-chunk
+// record counts where the caller's temp layout puts them (ChunkTemp / FrameTemp, temp_layout.h)
 hipError_t lzh_launch_lz4_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                int stage_mask, hipStream_t s, uint64_t frame_size = 0, uint32_t bpf = 1);
+                                uint64_t rec_stride, uint32_t* hdr, int stage_mask, hipStream_t s,
+                                uint64_t frame_size = 0, uint32_t bpf = 1);
 size_t lzh_lz4_rec_stride(uint64_t chunk_size);
 hipError_t lzh_launch_snappy_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                                    uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                   int stage_mask, hipStream_t s);
+                                   uint64_t rec_stride, uint32_t* hdr, int stage_mask, hipStream_t s);
 size_t lzh_snappy_rec_stride(uint64_t chunk_size);
 uint32_t lzh_snappy_frags(uint64_t chunk_size);
+// the emit kernel of a snappy launcher by waves per block: k1 for chunks of one fragment, else the kernel with
+// kW >= min(frags, 8) waves (the block has exactly that many); args: the kernels' common arguments
+template <class K1, class K2, class K4, class K8, class... Args>
+void lzh_launch_snappy_emit(K1 k1, K2 k2, K4 k4, K8 k8, uint32_t frags, uint32_t nchunks, hipStream_t s, Args... args) {
+    const uint32_t W = frags < 8 ? frags : 8;
+    if (W <= 1) hipLaunchKernelGGL(k1, dim3(nchunks), dim3(64), 0, s, args...);
+    else if (W == 2) hipLaunchKernelGGL(k2, dim3(nchunks), dim3(128), 0, s, args...);
+    else if (W <= 4) hipLaunchKernelGGL(k4, dim3(nchunks), dim3(64 * W), 0, s, args...);
+    else hipLaunchKernelGGL(k8, dim3(nchunks), dim3(64 * W), 0, s, args...);
+}
 
 // ragged batches (ragged_hip.hip, pack_hip.hip): chunk i = in_bytes[i] bytes at in_ptrs[i] (device arrays), every
-// slot sized for max_bytes (staging: stride; records: lzh_*_rec_stride(max_bytes), then the per-chunk record
-// counts as in the split launchers above); a chunk larger than max_bytes gets csizes[i] = 0
+// slot sized for max_bytes (chunk_temp(codec, nchunks, max_bytes) of temp_layout.h lays them out); a chunk larger
+// than max_bytes gets csizes[i] = 0
 hipError_t lzh_launch_lz4_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
                                  uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                 hipStream_t s);
+                                 uint64_t rec_stride, uint32_t* hdr, hipStream_t s);
 hipError_t lzh_launch_snappy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
                                     uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                    hipStream_t s);
+                                    uint64_t rec_stride, uint32_t* hdr, hipStream_t s);
 hipError_t lzh_launch_pack_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
                                   const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
                                   uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s);

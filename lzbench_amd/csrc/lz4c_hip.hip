@@ -1636,6 +1636,7 @@ lzh_lz4f_linked_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable
 }
 
 #endif
+#include "../../include/lzbench_hip.h"
 #include "launch.h"
 size_t lzh_lz4_rec_stride(uint64_t chunk_size) { return ((chunk_size / 4 + 4) * 8 + 255) / 256 * 256; }
 
@@ -1648,15 +1649,14 @@ hipError_t lzh_launch_lz4_compress_v2(const uint8_t* in, uint64_t n_total, uint6
     return hipGetLastError();
 }
 
-// parse kernel + emit kernel (records in `recs`: nchunks x rec_stride bytes, then 8 bytes per chunk);
+// parse kernel + emit kernel (records in `recs`: nchunks x rs bytes; 8 bytes per chunk at `hdr`);
 // stage_mask bit 0 = parse, bit 1 = emit (profiling runs one of them)
 hipError_t lzh_launch_lz4_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                int stage_mask, hipStream_t s, uint64_t frame_size, uint32_t bpf) {
+                                uint64_t rs, uint32_t* hdr, int stage_mask, hipStream_t s, uint64_t frame_size,
+                                uint32_t bpf) {
     if (nchunks == 0) return hipSuccess;
     if (bpf <= 1) { bpf = 1; frame_size = chunk_size; }
-    const uint64_t rs = lzh_lz4_rec_stride(chunk_size);
-    uint32_t* hdr = (uint32_t*)(recs + rs * nchunks);
     if (stage_mask & 1)
         hipLaunchKernelGGL(lzh_lz4_parse_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable, chunk_size,
                            acc, recs, rs, hdr, frame_size, bpf);
@@ -1683,7 +1683,7 @@ hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t 
 extern "C" int lzh_debug_lz4_stats(const void* d_in, uint64_t n, uint64_t in_readable, uint64_t chunk_size, int acc,
                                    void* d_stage, uint32_t* d_csizes, unsigned long long* d_stats, void* stream) {
     const uint64_t k = (n + chunk_size - 1) / chunk_size;
-    const uint64_t stride = ((chunk_size + chunk_size / 255 + 16 + 16) + 255) / 256 * 256;
+    const uint64_t stride = lzh_stage_stride(LZH_CODEC_LZ4, chunk_size);
     hipLaunchKernelGGL(lzh_lz4_compress_stats_kernel, dim3((unsigned)k), dim3(64), 0, (hipStream_t)stream,
                        (const uint8_t*)d_in, n, in_readable, chunk_size, acc, (uint8_t*)d_stage, stride, d_csizes, 0u,
                        d_stats);

@@ -209,17 +209,9 @@ hipError_t lzh_launch_snappy_compact(const void* const* in_ptrs, const uint64_t*
     if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lzh_snappy_parse_compact_kernel, dim3(nchunks * frags), dim3(64), 0, s, in_ptrs, in_bytes,
                        max_bytes, recs, hdr, frags, L);
-    const uint32_t W = frags < 8 ? frags : 8;
-#define LZH_SNE_ARGS in_ptrs, in_bytes, max_bytes, (const uint8_t*)recs, (const uint32_t*)hdr, stage, csizes, frags, L
-    if (W <= 1)
-        hipLaunchKernelGGL(lzh_snappy_emit_compact_kernel, dim3(nchunks), dim3(64), 0, s, LZH_SNE_ARGS);
-    else if (W == 2)
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_compact_kernel<2>, dim3(nchunks), dim3(128), 0, s, LZH_SNE_ARGS);
-    else if (W <= 4)
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_compact_kernel<4>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-    else
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_compact_kernel<8>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-#undef LZH_SNE_ARGS
+    lzh_launch_snappy_emit(lzh_snappy_emit_compact_kernel, lzh_snappy_emit_frag_compact_kernel<2>,
+                           lzh_snappy_emit_frag_compact_kernel<4>, lzh_snappy_emit_frag_compact_kernel<8>, frags, nchunks, s,
+                           in_ptrs, in_bytes, max_bytes, recs, hdr, stage, csizes, frags, L);
     return hipGetLastError();
 }
 

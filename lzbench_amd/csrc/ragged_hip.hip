@@ -154,10 +154,8 @@ lzh_ragged_desc_kernel(const uint64_t* offsets, const uint32_t* csizes, void* co
 
 hipError_t lzh_launch_lz4_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
                                  uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                 hipStream_t s) {
+                                 uint64_t rs, uint32_t* hdr, hipStream_t s) {
     if (nchunks == 0) return hipSuccess;
-    const uint64_t rs = lzh_lz4_rec_stride(max_bytes);
-    uint32_t* hdr = (uint32_t*)(recs + rs * nchunks);
     hipLaunchKernelGGL(lzh_lz4_parse_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes, acc,
                        recs, rs, hdr);
     hipLaunchKernelGGL(lzh_lz4_emit_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
@@ -169,25 +167,15 @@ uint32_t lzh_snappy_ragged_frags(uint64_t max_bytes) { return std::max(1u, lzh_s
 
 hipError_t lzh_launch_snappy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
                                     uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                    hipStream_t s) {
+                                    uint64_t rs, uint32_t* hdr, hipStream_t s) {
     if (nchunks == 0) return hipSuccess;
-    const uint64_t rs = lzh_snappy_rec_stride(max_bytes);
-    uint32_t* hdr = (uint32_t*)(recs + rs * nchunks);
     const uint32_t frags = lzh_snappy_ragged_frags(max_bytes);
     if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lzh_snappy_parse_ragged_kernel, dim3(nchunks * frags), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
                        recs, rs, hdr, frags);
-    const uint32_t W = frags < 8 ? frags : 8;
-#define LZH_SNE_ARGS in_ptrs, in_bytes, max_bytes, (const uint8_t*)recs, rs, (const uint32_t*)hdr, stage, stride, csizes, frags
-    if (W <= 1)
-        hipLaunchKernelGGL(lzh_snappy_emit_ragged_kernel, dim3(nchunks), dim3(64), 0, s, LZH_SNE_ARGS);
-    else if (W == 2)
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_ragged_kernel<2>, dim3(nchunks), dim3(128), 0, s, LZH_SNE_ARGS);
-    else if (W <= 4)
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_ragged_kernel<4>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-    else
-        hipLaunchKernelGGL(lzh_snappy_emit_frag_ragged_kernel<8>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-#undef LZH_SNE_ARGS
+    lzh_launch_snappy_emit(lzh_snappy_emit_ragged_kernel, lzh_snappy_emit_frag_ragged_kernel<2>,
+                           lzh_snappy_emit_frag_ragged_kernel<4>, lzh_snappy_emit_frag_ragged_kernel<8>, frags, nchunks, s,
+                           in_ptrs, in_bytes, max_bytes, recs, rs, hdr, stage, stride, csizes, frags);
     return hipGetLastError();
 }
 

@@ -1303,31 +1303,21 @@ size_t lzh_snappy_rec_stride(uint64_t chunk_size) {
     return ((chunk_size / 4 + 8) * 8 + 255) / 256 * 256;
 }
 
-// parse kernel + emit kernel (records: nchunks x rec_stride bytes, then a u32 count per chunk);
+// parse kernel + emit kernel (records in `recs`: nchunks x rs bytes; a u32 count per fragment at `hdr`);
 // stage_mask bit 0 = parse, bit 1 = emit
 hipError_t lzh_launch_snappy_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                                    uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                   int stage_mask, hipStream_t s) {
+                                   uint64_t rs, uint32_t* hdr, int stage_mask, hipStream_t s) {
     if (nchunks == 0) return hipSuccess;
-    const uint64_t rs = lzh_snappy_rec_stride(chunk_size);
-    uint32_t* hdr = (uint32_t*)(recs + rs * nchunks);
     const uint32_t frags = lzh_snappy_frags(chunk_size);
     if (stage_mask & 1)
         hipLaunchKernelGGL(lzh_snappy_parse_kernel, dim3(nchunks * frags), dim3(64), 0, s, in, n_total, in_readable,
                            chunk_size, recs, rs, hdr, frags);
     if (stage_mask & 2) {
         if (frags > (uint32_t)sne::kMaxFrags) return hipErrorInvalidValue;
-        const uint32_t W = frags < 8 ? frags : 8;
-#define LZH_SNE_ARGS in, n_total, in_readable, chunk_size, (const uint8_t*)recs, rs, (const uint32_t*)hdr, stage, stride, csizes, frags
-        if (W <= 1)
-            hipLaunchKernelGGL(lzh_snappy_emit_kernel, dim3(nchunks), dim3(64), 0, s, LZH_SNE_ARGS);
-        else if (W == 2)
-            hipLaunchKernelGGL(lzh_snappy_emit_frag_kernel<2>, dim3(nchunks), dim3(128), 0, s, LZH_SNE_ARGS);
-        else if (W <= 4)
-            hipLaunchKernelGGL(lzh_snappy_emit_frag_kernel<4>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-        else
-            hipLaunchKernelGGL(lzh_snappy_emit_frag_kernel<8>, dim3(nchunks), dim3(64 * W), 0, s, LZH_SNE_ARGS);
-#undef LZH_SNE_ARGS
+        lzh_launch_snappy_emit(lzh_snappy_emit_kernel, lzh_snappy_emit_frag_kernel<2>, lzh_snappy_emit_frag_kernel<4>,
+                               lzh_snappy_emit_frag_kernel<8>, frags, nchunks, s, in, n_total, in_readable, chunk_size,
+                               recs, rs, hdr, stage, stride, csizes, frags);
     }
     return hipGetLastError();
 }

@@ -1,0 +1,164 @@
+// lzbench_amd/csrc/temp_layout.h -- where everything lives in the caller's d_temp (host only, for api.cpp).
+//
+// Every call of the device API carves its temp buffer with one of the functions below, and the matching
+// *_temp_bytes function returns the same struct's `total`: the size promised to the caller and the offsets the
+// kernels are handed cannot disagree.  A layout is built with a TempCursor, so its regions are disjoint, in the
+// order they are taken, and each starts at a multiple of 256.  The spare 256 bytes after most regions (kGap) are
+// part of the published sizes (tests/golden/sizing.json) and addressed by nobody.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/lzbench_hip.h"
+#include "launch.h"
+#include "ragged_slots.h"
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// LZ4 / snappy chunks up to this size compress in two kernels (parse -> 8-byte sequence records -> emit);
+// larger ones (24-bit record fields) in the single kernel that assembles the block itself
+static const size_t kLz4SplitMax = (size_t)16 << 20;
+
+struct TempCursor {
+    size_t at = 0;
+    // the offset of the next region: `bytes` rounded up to 256, then `gap` spare bytes
+    size_t take(size_t bytes, size_t gap = 0) { return take_sized(align_up(bytes, 256) + gap); }
+    // a region whose size another file computes for its own carving (zstdc_hip.hip, decode_hip.hip): as it is
+    size_t take_sized(size_t bytes) { const size_t o = at; at += bytes; return o; }
+};
+static const size_t kGap = 256;
+
+// ---- compression of k chunks of up to `chunk` bytes (uniform calls: k = lzh_num_chunks(n, chunk); ragged
+// uniform-slot batches: k = nchunks, chunk = max_chunk_bytes):
+//   k staging slots of `stride` | split (LZ4 / snappy up to kLz4SplitMax): k record slots of `rec_stride` at
+//   `recs`, then the per-chunk record counts at `hdr` (LZ4: 8 bytes a chunk; snappy: a u32 per fragment)
+//                               | zstd: k per-frame scratch areas of the two zstd kernels at `recs`, worst level
+struct ChunkTemp {
+    bool split;
+    size_t stride, rec_stride, stage, recs, hdr, total;
+};
+static inline ChunkTemp chunk_temp(int codec, size_t k, size_t chunk) {
+    ChunkTemp t = {};
+    TempCursor c;
+    t.split = (codec == LZH_CODEC_LZ4 || codec == LZH_CODEC_SNAPPY) && chunk <= kLz4SplitMax;
+    t.stride = lzh_stage_stride(codec, chunk);
+    t.stage = c.take(k * t.stride, kGap);
+    t.recs = t.hdr = c.at;
+    if (t.split) {
+        t.rec_stride = codec == LZH_CODEC_LZ4 ? lzh_lz4_rec_stride(chunk) : lzh_snappy_rec_stride(chunk);
+        t.recs = c.take(k * t.rec_stride);
+        t.hdr = c.take(codec == LZH_CODEC_LZ4 ? k * 8 : k * 4 * lzh_snappy_ragged_frags(chunk), kGap);
+    } else if (codec == LZH_CODEC_ZSTD) {
+        for (int lv : {1, 2, -1, -2}) t.rec_stride = std::max(t.rec_stride, lzh_zstd_scratch_stride(chunk, lv));
+        t.recs = c.take_sized(k * t.rec_stride + kGap);
+    }
+    t.total = c.at;
+    return t;
+}
+
+// ---- framed compression: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes:
+//   staging slots | LZ4 sequence records of the blocks, then 8 bytes per block (linked frames: the per-frame
+//   table snapshots instead) | block sizes | block offsets inside their frame
+struct FrameGeo {
+    size_t F, bs, nframes, nblocks;
+    uint32_t bpf;
+};
+static inline FrameGeo frame_geo(size_t B, size_t n, size_t F) {
+    FrameGeo g;
+    g.F = F;
+    g.bs = std::min(F, B);
+    g.bpf = (uint32_t)((F + g.bs - 1) / g.bs);
+    g.nframes = lzh_num_chunks(n, F);
+    if (n == 0) {
+        g.nblocks = 0;
+    } else {
+        const size_t last = n - (g.nframes - 1) * F;
+        g.nblocks = (g.nframes - 1) * g.bpf + (last + g.bs - 1) / g.bs;
+    }
+    return g;
+}
+
+struct FrameTemp { size_t stride, rec_stride, stage, recs, hdr, bcs, rel, total; };
+static inline FrameTemp frame_temp(const FrameGeo& g) {
+    FrameTemp t;
+    TempCursor c;
+    t.stride = lzh_stage_stride(LZH_CODEC_LZ4, g.bs);
+    t.rec_stride = lzh_lz4_rec_stride(g.bs);
+    t.stage = c.take(g.nblocks * t.stride, kGap);
+    t.recs = c.take(g.nblocks * t.rec_stride);
+    t.hdr = c.take(g.nblocks * 8, kGap);
+    t.bcs = c.take(g.nblocks * 4, kGap);
+    t.rel = c.take(g.nblocks * 4, kGap);
+    t.total = c.at;
+    return t;
+}
+
+// ---- ragged compression, compact layout: every chunk's slots sized from its own size (ragged_slots.h):
+//   staging region | record region, then the per-chunk record counts (sized for max_bytes as in chunk_temp)
+//   | staging-slot sizes | record-slot sizes (u32 each) | staging-slot offsets | record-slot offsets
+//   (nchunks + 1 u64 each, scanned on the device)
+struct CompactTemp {
+    LzhCompactRegions reg;
+    size_t stage, recs, hdr, stage_sz, rec_sz, stage_off, rec_off, total;
+};
+static inline CompactTemp compact_temp(int codec, size_t total_in, size_t max_bytes, size_t nchunks) {
+    CompactTemp t;
+    TempCursor c;
+    t.reg = lzh_compact_regions(codec, total_in, max_bytes, nchunks);
+    t.stage = c.take(t.reg.stage, kGap);
+    t.recs = c.take(t.reg.recs);
+    t.hdr = c.take(codec == LZH_CODEC_LZ4 ? nchunks * 8 : nchunks * 4 * lzh_snappy_ragged_frags(max_bytes), kGap);
+    t.stage_sz = c.take(nchunks * 4);
+    t.rec_sz = c.take(nchunks * 4);
+    t.stage_off = c.take((nchunks + 1) * 8);
+    t.rec_off = c.take((nchunks + 1) * 8, kGap);
+    t.total = c.at;
+    return t;
+}
+
+// ---- decompression: the scanned offsets (k + 1 u64, used when the caller passes none), then
+//   frames: maxbpf block descriptors per frame (32 bytes each) | block statuses | frame statuses
+//   zstd, snappy: the temp of the split decoder (decode_hip.hip carves it), where there is one
+//   ragged: a block descriptor per chunk
+// need_scan: the smallest temp that holds the scanned offsets.  need_split: the smallest temp with which the split
+// decoder runs (0: this codec and chunk size have none); a smaller temp decodes every chunk whole.
+struct DecodeTemp { size_t scan, desc, bstat, fstat, split, need_scan, need_split, total; };
+
+// decode side of a framed layout: maxbpf descriptor slots per frame (blocks of 64 KiB / 32 KiB at the least)
+static inline uint32_t frame_maxbpf(int codec, size_t F) {
+    const size_t bmin = codec == LZH_CODEC_LZ4F ? 65536 : 32768;
+    return (uint32_t)std::max<size_t>(1, (F + bmin - 1) / bmin);
+}
+
+static inline DecodeTemp decode_temp(int codec, size_t n, size_t chunk) {
+    DecodeTemp t = {};
+    TempCursor c;
+    const size_t k = lzh_num_chunks(n, chunk);
+    t.scan = c.take((k + 1) * sizeof(uint64_t));
+    t.need_scan = c.at + kGap;
+    if (codec == LZH_CODEC_LZ4F || codec == LZH_CODEC_NVLZ4) {
+        const size_t nd = k * frame_maxbpf(codec, chunk);
+        t.desc = c.take(nd * 32);
+        t.bstat = c.take(nd * 4);
+        t.fstat = c.take(k * 4, kGap);
+    } else if (codec == LZH_CODEC_ZSTD || codec == LZH_CODEC_SNAPPY) {
+        const size_t bytes = codec == LZH_CODEC_ZSTD ? lzh_zstd_decode_temp(n, chunk) : lzh_snappy_split_temp(n, chunk);
+        t.split = c.take_sized(bytes);
+        // (the zstd call has always asked for the whole sizing answer, the snappy call for the split's own bytes)
+        if (bytes) t.need_split = codec == LZH_CODEC_ZSTD ? c.at + kGap : c.at;
+    }
+    t.total = c.at + kGap;
+    return t;
+}
+
+static inline DecodeTemp ragged_decode_temp(size_t nchunks) {
+    DecodeTemp t = {};
+    TempCursor c;
+    t.scan = c.take((nchunks + 1) * sizeof(uint64_t), kGap);
+    t.need_scan = c.at;   // (the ragged call asks for the whole of `total`)
+    t.desc = c.take(nchunks * 32, kGap);
+    t.total = c.at;
+    return t;
+}
