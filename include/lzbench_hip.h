@@ -158,7 +158,8 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
  * d_out_bytes are device arrays of nchunks entries; nothing here synchronises with the host or reads a size
  * back, so the calls can be captured in a stream like the uniform ones.
  * Codecs: LZH_CODEC_LZ4 (level = acceleration, as above) and LZH_CODEC_SNAPPY; zstd, the LZ4 frame, the
- * nvcomp container and memcpy return LZH_EARG for now (so do their sizing functions: 0).
+ * nvcomp container and memcpy return LZH_EARG (so do their sizing functions: 0).  zstd has entry points of
+ * its own, section 3c below; the five functions of this section keep refusing LZH_CODEC_ZSTD.
  * Output: as the uniform compress call writes it -- d_csizes[i], d_offsets[0 .. nchunks] ([nchunks] = the packed
  * total), chunks packed contiguously in index order, a chunk whose compressed size equals its size stored raw; equal
  * sizes over contiguous inputs give the uniform call's bytes.  A zero-length chunk is legal (the one-byte LZ4
@@ -226,6 +227,49 @@ int lzh_debug_ragged_compact_slots(int codec, const uint64_t* sizes, size_t nchu
  * staging region, out[2], out[3] = of the record region.  Host arithmetic only; LZH_EARG as above. */
 int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                      uint64_t* out);
+
+/* ---- 3c. ragged zstd batches ------------------------------------------------------------ */
+/* lzh_compress_ragged_async / lzh_decompress_ragged_async for zstd frames (LZH_CODEC_ZSTD above), under names of
+ * their own.  The contract is that of 3b: chunk i is the d_in_bytes[i] bytes at d_in_ptrs[i], any alignment, chunks
+ * may overlap or repeat; every input chunk needs 16 readable bytes after it; max_chunk_bytes bounds every
+ * d_in_bytes[i] / d_out_bytes[i] and is at most 16 MiB, else LZH_EARG; nchunks == 0 returns LZH_OK and launches
+ * nothing; the checks (level / max_chunk_bytes, null pointers, then temp_bytes below the sizing answer:
+ * LZH_ESPACE) come before any device call; the sizing functions are host arithmetic and non-decreasing in
+ * max_chunk_bytes, nchunks and total_in_bytes.  A chunk whose device-side size is larger than max_chunk_bytes is not
+ * processed and no kernel touches its slots: d_csizes[i] = 0 (no packed bytes) on compression, d_status[i] = -1 on
+ * decompression.  packed_cap is enforced on the device by the pack kernel (a chunk whose packed range would pass it
+ * is not written) and d_offsets[nchunks] > packed_cap reports an incomplete output.  d_offsets of the decompress
+ * call may be NULL (derived from d_csizes into d_temp).  A chunk whose compressed size equals its size is stored
+ * raw, on both sides.
+ * Frame i: chunk i becomes the frame lzbench's zstd row writes for a chunk of that size alone
+ * (ZSTD_getParams(level, size, 0), content size, no checksum) -- the bytes lzh_compress_async(LZH_CODEC_ZSTD, level,
+ * ..., n = size, chunk_size >= size) writes; equal sizes over contiguous input give the uniform call's d_csizes,
+ * d_offsets and packed bytes.  A zero-length chunk is legal: the 9-byte frame of an empty input.
+ * Levels: accepted exactly when lzh_level_supported(LZH_CODEC_ZSTD, level, max_chunk_bytes) is 1 (level 2 only for
+ * max_chunk_bytes <= 131072: above that some size's row is double-fast); else LZH_EARG, and the compress sizing
+ * function returns 0.
+ * Compress temp: nchunks staging slots, then nchunks scratch areas of the two zstd kernels (sequences, literals,
+ * a block attempt, a Huffman stream, the hash table), every one sized for max_chunk_bytes: nchunks x (the staging
+ * stride + the scratch stride of max_chunk_bytes; 1.26 MiB a chunk at 128 KiB, 278 KiB at 16 KiB), so a skewed
+ * batch pays for its largest chunk nchunks times.  There is no compact layout for zstd.  Decompress temp: the
+ * scanned offsets (as 3b).
+ * lzh_zstd_ragged_max_packed_bytes: zstd expands small chunks (1..64 bytes become size + 9, which is not stored
+ * raw); the bound is the sum of the per-chunk bounds lzh_stage_stride(LZH_CODEC_ZSTD, .) is sized for.
+ * Decoding: every frame in the one-wave decoder of lzh_decompress_async (any frame of lzbench's shape, also with
+ * the content checksum; the verdicts of that call); the four-kernel decoder does not take ragged batches yet.
+ * Streams: every launch goes on hip_stream -- no side stream, event, host synchronisation or size read back (the
+ * uniform zstd calls fork to side streams) -- so a captured call has no parallel branches. */
+size_t lzh_zstd_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_zstd_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_zstd_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks);
+int lzh_zstd_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                   size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                                   uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                                   void* hip_stream);
+int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                     const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                     size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                     size_t temp_bytes, void* hip_stream);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

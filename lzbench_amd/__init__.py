@@ -99,6 +99,11 @@ SIGNATURES = {
     "lzh_ragged_max_packed_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
     "lzh_compress_ragged_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_decompress_ragged_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_zstd_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
+    "lzh_zstd_ragged_decompress_temp_bytes": (_SZ, [_SZ, _SZ]),
+    "lzh_zstd_ragged_max_packed_bytes": (_SZ, [_SZ, _SZ]),
+    "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
     "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
@@ -369,7 +374,7 @@ class DeviceCodec:
 
 
 class RaggedCodec:
-    """Device-resident codec over ragged batches (include/lzbench_hip.h 3b): chunk i of a batch is
+    """Device-resident codec over ragged batches (include/lzbench_hip.h 3b; zstd: 3c): chunk i of a batch is
     sizes[i] bytes at offsets[i] of a flat uint8 CUDA tensor, any alignment, in any order.
 
     Buffers are sized once for max_chunks chunks of up to max_chunk_bytes; max_total_bytes bounds a
@@ -380,6 +385,9 @@ class RaggedCodec:
     max_total_bytes (about 3.2 x) plus some 600 bytes per chunk, the output is the same, and a batch
     must keep its total within max_total_bytes (checked on the host by compress(); compress_arrays()
     leaves a chunk whose slots do not fit uncompressed with csizes[i] = 0).
+    zstd / zstd_fast (the fast-strategy levels lzh_level_supported accepts for max_chunk_bytes) go through the
+    lzh_zstd_*_ragged calls: one frame per chunk, a staging slot and a scratch area of the zstd kernels per chunk,
+    each sized for max_chunk_bytes; compact=True raises ValueError (there is no compact layout for zstd).
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
@@ -393,16 +401,27 @@ class RaggedCodec:
         self.max_total = max_chunks * max_chunk_bytes if max_total_bytes is None else max_total_bytes
         L = lib()
         self.compact = compact
-        if compact:
+        self.zstd = self.codec == LZH_CODEC_ZSTD
+        if self.zstd and compact:
+            raise ValueError("ragged batches: zstd has no compact layout")
+        if self.zstd:
+            ct = L.lzh_zstd_ragged_compress_temp_bytes(self.level, max_chunk_bytes, max_chunks)
+            dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
+        elif compact:
             ct = L.lzh_ragged_compact_compress_temp_bytes(self.codec, self.max_total, max_chunk_bytes, max_chunks)
         else:
             ct = L.lzh_ragged_compress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
-        dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
+        if not self.zstd:
+            dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
         if ct == 0 or dt == 0:
-            raise ValueError(f"ragged batches: codec {codec} / chunks of {max_chunk_bytes} bytes are not supported")
+            raise ValueError(f"ragged batches: codec {codec} (level {self.level}) / chunks of {max_chunk_bytes} bytes "
+                             "are not supported")
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
         u8 = dict(dtype=torch.uint8, device=self.dev)
-        self.max_packed = L.lzh_ragged_max_packed_bytes(self.codec, self.max_total, max_chunks)
+        if self.zstd:
+            self.max_packed = L.lzh_zstd_ragged_max_packed_bytes(self.max_total, max_chunks)
+        else:
+            self.max_packed = L.lzh_ragged_max_packed_bytes(self.codec, self.max_total, max_chunks)
         self.packed = torch.empty(self.max_packed + 64, **u8)
         self.csizes = torch.empty(max_chunks, dtype=torch.int32, device=self.dev)
         self.offsets = torch.empty(max_chunks + 1, dtype=torch.int64, device=self.dev)
@@ -440,14 +459,18 @@ class RaggedCodec:
         self.k = k
         out = (self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
                self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
-        if self.compact:
+        if self.zstd:
+            rc = lib().lzh_zstd_compress_ragged_async(self.level, d[0].data_ptr(), d[1].data_ptr(), k,
+                                                      self.max_chunk_bytes, *out)
+        elif self.compact:
             rc = lib().lzh_compress_ragged_compact_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
                                                          self.max_chunk_bytes, self.max_total, *out)
         else:
             rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
                                                  self.max_chunk_bytes, *out)
         if rc:
-            raise RuntimeError(f"lzh_compress_ragged{'_compact' if self.compact else ''}_async failed ({rc})")
+            name = "lzh_zstd_compress_ragged" if self.zstd else f"lzh_compress_ragged{'_compact' if self.compact else ''}"
+            raise RuntimeError(f"{name}_async failed ({rc})")
 
     def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:
         """Decode chunk i to out_buf[out_offsets[i] : out_offsets[i] + out_sizes[i]]; self.status[i] = its
@@ -463,12 +486,15 @@ class RaggedCodec:
         csizes = self.csizes if csizes is None else csizes
         self._out = d
         self.k = k
-        rc = lib().lzh_decompress_ragged_async(self.codec, packed.data_ptr(), packed.numel(), csizes.data_ptr(),
-                                               offsets.data_ptr() if offsets is not None else None, d[0].data_ptr(),
-                                               d[1].data_ptr(), k, self.max_chunk_bytes, self.status.data_ptr(),
-                                               self.dtemp.data_ptr(), self.dtemp.numel(), self._stream())
+        args = (packed.data_ptr(), packed.numel(), csizes.data_ptr(), offsets.data_ptr() if offsets is not None else None,
+                d[0].data_ptr(), d[1].data_ptr(), k, self.max_chunk_bytes, self.status.data_ptr(), self.dtemp.data_ptr(),
+                self.dtemp.numel(), self._stream())
+        if self.zstd:
+            rc = lib().lzh_zstd_decompress_ragged_async(*args)
+        else:
+            rc = lib().lzh_decompress_ragged_async(self.codec, *args)
         if rc:
-            raise RuntimeError(f"lzh_decompress_ragged_async failed ({rc})")
+            raise RuntimeError(f"lzh_{'zstd_' if self.zstd else ''}decompress_ragged_async failed ({rc})")
 
     def packed_total(self) -> int:
         return int(self.offsets[self.k].item())

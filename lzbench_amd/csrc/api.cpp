@@ -383,6 +383,81 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
     return LZH_OK;
 }
 
+// ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
+// compress temp: chunk_temp(zstd) of nchunks staging slots and scratch areas sized for max_chunk_bytes;
+// decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors)
+
+static bool zstd_ragged_ok(int level, size_t max_chunk_bytes) {
+    return max_chunk_bytes <= kLz4SplitMax && lzh_level_supported(LZH_CODEC_ZSTD, level, max_chunk_bytes) == 1;
+}
+
+// (a batch of empty chunks is laid out as one of 1-byte chunks, here and in lzh_launch_zstd_ragged: size 0 is
+// ZSTD_getParams' "unknown size", whose parameters would size every slot for a full 128 KiB block)
+static ChunkTemp zstd_ragged_temp(size_t nchunks, size_t max_chunk_bytes) {
+    return chunk_temp(LZH_CODEC_ZSTD, nchunks, std::max<size_t>(max_chunk_bytes, 1));
+}
+
+size_t lzh_zstd_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_ragged_ok(level, max_chunk_bytes) ? zstd_ragged_temp(nchunks, max_chunk_bytes).total : 0;
+}
+
+size_t lzh_zstd_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks) {
+    return max_chunk_bytes <= kLz4SplitMax ? ragged_decode_temp(nchunks).total : 0;
+}
+
+size_t lzh_zstd_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks) {
+    // the sum of codec_bound (the bound lzh_stage_stride sizes a slot for) over the chunks, whatever their sizes:
+    // size + size / 256 + at most codec_bound(0) = 64 (a chunk of 1..64 bytes becomes size + 9 and is not stored
+    // raw); then the uniform call's 8 bytes per chunk and 64
+    return total_in_bytes + (total_in_bytes >> 8) + nchunks * (codec_bound(LZH_CODEC_ZSTD, 0) + 8) + 64;
+}
+
+int lzh_zstd_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                   size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                   uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
+    if (nchunks > 0x7fffffffu) return LZH_EARG;   // launch grids
+    const ChunkTemp t = zstd_ragged_temp(nchunks, max_chunk_bytes);
+    if (temp_bytes < t.total) return LZH_ESPACE;
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    {
+        Range range("lzh:compress_kernel");
+        LZH_CHECK(lzh_launch_zstd_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes,
+                                         k, base + t.recs, t.rec_stride, s));
+    }
+    Range range("lzh:scan_pack");
+    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
+    LZH_CHECK(lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                     d_offsets, (uint8_t*)d_packed, packed_cap, k, s));
+    return LZH_OK;
+}
+
+int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                     const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                     size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                     size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_packed || !d_csizes || !d_out_ptrs || !d_out_bytes || !d_status || !d_temp) return LZH_EARG;
+    if (nchunks > 0x7fffffffu) return LZH_EARG;
+    const DecodeTemp t = ragged_decode_temp(nchunks);
+    if (temp_bytes < t.total) return LZH_ESPACE;
+    Range range("lzh:decompress");
+    const uint64_t* offs = d_offsets;
+    if (!offs) {
+        LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)((uint8_t*)d_temp + t.scan), nullptr, s));
+        offs = (const uint64_t*)((uint8_t*)d_temp + t.scan);
+    }
+    LZH_CHECK(lzh_launch_zstd_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
+                                                d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, s));
+    return LZH_OK;
+}
+
 // ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h); compact_temp
 // lays the temp out for the sizing call, the async call and the host mirror ----
 size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks) {

@@ -21,7 +21,7 @@
 #endif
 #if LZH_DEC_STATS
 __shared__ unsigned long long g_dst[16];
-__device__ unsigned long long lzh_dec_stats_buf[16];
+LZH_TU_VAR __device__ unsigned long long lzh_dec_stats_buf[16];
 #define DST(i, v) do { if (threadIdx.x == 0) g_dst[i] += (unsigned long long)(v); } while (0)
 #define DCLK(t) const uint64_t t = __builtin_amdgcn_s_memtime()
 #else
@@ -726,6 +726,7 @@ __device__ __forceinline__ void decompress_chunk(LDSA uint8_t* win, int codec, c
 #endif
 }
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (zstd_ragged_decode_hip.hip includes this file for its device functions alone)
 // output window | start marks | input ring
 #define LZH_DEC_KERNEL(NAME, KW)                                                                            \
     extern "C" __global__ void __launch_bounds__(64)                                                       \
@@ -788,6 +789,7 @@ lzh_decompress_linked_kernel(const uint8_t* packed, uint64_t packed_readable, ui
         }
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------------
 // Snappy chunks of more than one 64 KiB fragment, decoded a fragment per wave.  The reference
@@ -811,6 +813,7 @@ constexpr uint32_t kMinFrags = 8;    // (by default; see lzh_snappy_split_temp)
 __host__ __device__ inline uint32_t frags(uint64_t chunk_size) { return (uint32_t)((chunk_size + 65535) >> kFragLog); }
 }
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_split_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                         const uint32_t* csizes, uint64_t n_total, uint64_t chunk_size, uint32_t F, uint32_t* desc,
@@ -947,6 +950,7 @@ extern "C" int lzh_debug_dec_stats(unsigned long long* host, int reset) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(lzh_dec_stats_buf), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
 }
 #endif
+#endif   // LZH_DEVICE_FUNCTIONS_ONLY
 
 // ---------------------------------------------------------------------------------------
 // zstd frames (RFC 8878), the decode side of lzbench's zstd rows (compressors.cpp:1767-1773:
@@ -1047,20 +1051,20 @@ constexpr int kHufLogMax = 12;          // HUF_TABLELOG_MAX (huf.h:119): the dec
 // literal-length / match-length codes: baseline and extra bits (RFC 8878 3.1.1.3.2.1.1;
 // common/zstd_internal.h LL_bits / ML_bits) and the predefined distributions (3.1.1.3.2.2;
 // LL/ML/OF_defaultNorm)
-__constant__ uint32_t kLLBase[36] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10,   11,   12,   13,    14,    15,    16,   18,
+LZH_TU_VAR __constant__ uint32_t kLLBase[36] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10,   11,   12,   13,    14,    15,    16,   18,
                                      20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536};
-__constant__ uint8_t kLLBits[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,  0,  0,  0,  1,  1,
+LZH_TU_VAR __constant__ uint8_t kLLBits[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,  0,  0,  0,  1,  1,
                                     1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-__constant__ uint32_t kMLBase[53] = {3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14,  15,  16,  17,  18,   19,   20,
+LZH_TU_VAR __constant__ uint32_t kMLBase[53] = {3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14,  15,  16,  17,  18,   19,   20,
                                      21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32,  33,  34,  35,  37,   39,   41,
                                      43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051, 4099, 8195, 16387, 32771, 65539};
-__constant__ uint8_t kMLBits[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+LZH_TU_VAR __constant__ uint8_t kMLBits[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                     0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-__constant__ int8_t kLLNorm[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
+LZH_TU_VAR __constant__ int8_t kLLNorm[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
                                    2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1};
-__constant__ int8_t kMLNorm[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1,  1,  1,  1,  1,  1,  1,  1,  1,  1,  1,
+LZH_TU_VAR __constant__ int8_t kMLNorm[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1,  1,  1,  1,  1,  1,  1,  1,  1,  1,  1,
                                    1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
-__constant__ int8_t kOFNorm[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
+LZH_TU_VAR __constant__ int8_t kOFNorm[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
 
 // FSE decoding-table cell, 32 bits: next-state base (9) | nbBits << 9 (4) | extra bits << 13 (5)
 // | symbol << 18 (6).  For LL/ML the symbol is the length code (its baseline comes from a constant
@@ -1608,7 +1612,7 @@ __device__ __forceinline__ int huf_streams(const Bytes& src, int pos, int csize,
 
 // HUF_selectDecoder (huf_decompress.c:1565-1615): 1 when the reference decodes a 4-stream literal
 // section it has just read a tree for with the double-symbol decoder (X2)
-__constant__ uint16_t kAlgoTime[16][4] = {
+LZH_TU_VAR __constant__ uint16_t kAlgoTime[16][4] = {
     {0, 0, 1, 1}, {0, 0, 1, 1}, {150, 216, 381, 119}, {170, 205, 514, 112}, {177, 199, 539, 110},
     {197, 194, 644, 107}, {221, 192, 735, 107}, {256, 189, 881, 106}, {359, 188, 1167, 109},
     {582, 187, 1570, 114}, {688, 187, 1712, 122}, {825, 186, 1965, 136}, {976, 185, 2131, 150},
@@ -2024,6 +2028,7 @@ __device__ __forceinline__ int decode_frame(const Bytes& rin, const Bytes& lout,
 
 }  // namespace zstdd
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (the rest of the file: the split decoder, the kernels, the launchers)
 // ---------------------------------------------------------------------------------------
 // zstd decoding in three kernels.  The sequence section's decoding chain (bit reader, three FSE
 // states, repcodes: ZSTD_decodeSequence, zstd_decompress_block.c:1169-1270) is serial within a
@@ -3693,3 +3698,4 @@ size_t lzh_zstd_decode_temp(uint64_t n, uint64_t chunk_size) {
     return k * Z.stride + zsplit::zdummy_bytes(k) + ((k * 4 + 255) & ~255ull) + ((k * sizeof(zsplit::ZFrame) + 255) & ~255ull) + 256 +
            k * Z.bmax * sizeof(zsplit::ZHuf) + 256 + ((k * 4 + 8 + 255) & ~255ull);   // (+ the plan's frame list, counts)
 }
+#endif   // LZH_DEVICE_FUNCTIONS_ONLY

@@ -40,6 +40,19 @@ hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_
                                     uint8_t* scratch, hipStream_t s);
 size_t lzh_zstd_scratch_stride(size_t chunk_size, int level);
 int lzh_zstd_level_ok(int level, size_t chunk_size);
+// dynamic LDS of the zstd match kernels for frames of up to chunk_size bytes (0: the hash table lives in scratch)
+uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size);
+// ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip; include/lzbench_hip.h 3c): chunk i =
+// in_bytes[i] bytes at in_ptrs[i]; staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes)
+// lays them out (fstride: its rec_stride, the scratch areas' distance, at least lzh_zstd_scratch_stride(max_bytes,
+// level)).  Every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 / status[i] = -1 and none of its
+// slots is touched.
+hipError_t lzh_launch_zstd_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
+                                  uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                  uint8_t* scratch, uint64_t fstride, hipStream_t s);
+hipError_t lzh_launch_zstd_decompress_ragged(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                                             const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
+                                             uint64_t max_bytes, int32_t* status, uint32_t nchunks, hipStream_t s);
 // frame_size / bpf: framed layouts (LZ4 frame, nvcomp container) -- block i is block i mod bpf of
 // frame i / bpf (frames of frame_size bytes cut into blocks of chunk_size); bpf <= 1: plain chunks
 hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,

@@ -256,7 +256,7 @@ __device__ void tab_put_pos(const Tab& T, const Bytes& in, int pos, const ZParam
 #define LZH_ZSTDC_STATS 0   // match / entropy kernel phase clocks (tools/zstdc_stats.py)
 #endif
 #if LZH_ZSTDC_STATS
-__device__ unsigned long long lzh_zstdc_stats_buf[24];
+LZH_TU_VAR __device__ unsigned long long lzh_zstdc_stats_buf[24];
 #endif
 // match-kernel phase clocks (indices 0..5: search batches, match, fills + repcodes, batches, sequences,
 // frames), accumulated in registers and added once per frame
@@ -607,6 +607,7 @@ __device__ void fast_block(const Tab& T, const Bytes& in, const ZParams& P, int 
 
 using namespace zc;
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (zstd_ragged_hip.hip includes this file for its device functions and kernel bodies alone)
 // one wave per frame; block k of every frame
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level,
@@ -618,71 +619,9 @@ lzh_zstd_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable,
     const uint64_t ioff = f * chunk_size;
     if (ioff >= n_total && !(n_total == 0 && f == 0)) return;
     const uint64_t nf = n_total ? min(chunk_size, n_total - ioff) : 0;
-    const ZParams P = params_for(level, nf);
-    if (!P.ok) return;
-    const uint64_t nblocks = nf ? (nf + P.bsize - 1) / P.bsize : 1;
-    if ((uint64_t)k >= nblocks) return;
-    uint8_t* fs = scratch + f * fstride;
-    rsrc_t hdr = make_rsrc(fs, 64);
-    const int bs = k * (int)P.bsize;
-    const int be = (int)min<uint64_t>(nf, (uint64_t)bs + P.bsize);
-    if (be - bs < 7) {                                   // ZSTD_buildSeqStore: too small, stored raw
-        if (lane == 0) { st_b32(hdr, 32, 1u); st_b32(hdr, 0, 0u); st_b32(hdr, 4, 0u); }
-        return;
-    }
-    Bytes in_b;
-    in_b.init(in + ioff, min<uint64_t>(in_readable - ioff, nf + 16));
-    SeqOut O;
-    O.seq = make_rsrc(fs + seq_off, (uint32_t)(lit_off - seq_off));
-    O.lits.init(fs + lit_off, P.bsize + 64);
-    O.ns = 0;
-    O.nl = 0;
-    uint32_t rep[2] = {1u, 4u};                          // repStartValue
-    if (k > 0) { rep[0] = uni(ld_b32(hdr, 16)); rep[1] = uni(ld_b32(hdr, 20)); }
-    const uint32_t tbytes = 4u << P.hlog;
-    const uint32_t nent = 1u << P.hlog;
-    const uint32_t lds_table_bytes = lds_arg;          // the table's bytes in dynamic LDS (0: global)
-    const uint32_t bmb = max(nent / 8u, 4u);            // LdsTab17 bitmap bytes
-    if (LZH_ZSTD_TAB17 && chunk_size <= 131072u && nblocks == 1 && 2u * nent + bmb <= lds_table_bytes) {
-        // (single-block frames: the table starts empty and is not saved)
-        LdsTab17 T{(LDSA uint16_t*)zlds, (LDSA uint32_t*)((LDSA uint8_t*)zlds + 2 * nent)};
-        for (uint32_t i = lane; i < (2u * nent + bmb) / 4u; i += 64) ((volatile LDSA uint32_t*)zlds)[i] = 0u;
-        T.fence();
-        if (P.mls == 6) fast_block<6>(T, in_b, P, bs, be, rep, O, lane);   // (hash fixed at compile time)
-        else if (P.mls == 5) fast_block<5>(T, in_b, P, bs, be, rep, O, lane);
-        else fast_block(T, in_b, P, bs, be, rep, O, lane);
-    } else if (chunk_size < (16u << 20) && 3u * nent <= lds_table_bytes) {
-        LdsTab24 T{(LDSA uint16_t*)zlds, (LDSA uint8_t*)zlds + 2 * nent};
-        rsrc_t save = make_rsrc(fs + tab_off, tbytes);
-        for (uint32_t i = lane; i < nent; i += 64) T.put(i, k == 0 ? 0u : ld_b32(save, (int)(i * 4)));
-        T.fence();
-        fast_block(T, in_b, P, bs, be, rep, O, lane);
-        if ((uint64_t)k + 1 < nblocks)
-            for (uint32_t i = lane; i < nent; i += 64) st_b32(save, (int)(i * 4), T.get(i));
-    } else if (tbytes <= lds_table_bytes) {
-        LdsTab T{(LDSA uint32_t*)zlds};
-        rsrc_t save = make_rsrc(fs + tab_off, tbytes);
-        for (uint32_t i = lane; i < tbytes / 4; i += 64) T.put(i, k == 0 ? 0u : ld_b32(save, (int)(i * 4)));
-        T.fence();
-        fast_block(T, in_b, P, bs, be, rep, O, lane);
-        if ((uint64_t)k + 1 < nblocks)
-            for (uint32_t i = lane; i < tbytes / 4; i += 64) st_b32(save, (int)(i * 4), T.get(i));
-    } else {
-        GlbTab T{make_rsrc(fs + tab_off, tbytes)};
-        if (k == 0) {
-            for (uint32_t i = lane; i < tbytes / 4; i += 64) T.put(i, 0u);
-            T.fence();
-        }
-        fast_block(T, in_b, P, bs, be, rep, O, lane);
-    }
-    if (lane == 0) {
-        st_b32(hdr, 0, (uint32_t)O.ns);
-        st_b32(hdr, 4, (uint32_t)O.nl);
-        st_b32(hdr, 8, rep[0]);
-        st_b32(hdr, 12, rep[1]);
-        st_b32(hdr, 32, 0u);
-    }
+#include "zstdc_match_body.inc"
 }
+#endif
 
 // ======================================================================= entropy stage
 namespace ze {
@@ -762,15 +701,15 @@ __device__ __forceinline__ uint32_t ll_bits(uint32_t ll) {
 __device__ __forceinline__ uint32_t ml_bits(uint32_t mb) {
     return mb < 32 ? 0u : mb < 40 ? 1u : mb < 48 ? 2u : mb < 64 ? 3u : mb < 96 ? 4u : mb < 128 ? 5u : (uint32_t)hb32(mb);
 }
-__device__ __constant__ uint8_t kLLB[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3,
+LZH_TU_VAR __device__ __constant__ uint8_t kLLB[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3,
                                             4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-__device__ __constant__ uint8_t kMLB[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+LZH_TU_VAR __device__ __constant__ uint8_t kMLB[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                             0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-__device__ __constant__ int16_t kLLDef[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
+LZH_TU_VAR __device__ __constant__ int16_t kLLDef[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
                                               2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1};
-__device__ __constant__ int16_t kMLDef[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
+LZH_TU_VAR __device__ __constant__ int16_t kMLDef[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
                                               1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
-__device__ __constant__ int16_t kOFDef[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
+LZH_TU_VAR __device__ __constant__ int16_t kOFDef[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
                                               -1, -1, -1, -1, -1};
 
 // ---- single-lane byte sinks: global (Bytes) or LDS, and a 64-bit bit accumulator (LSB first)
@@ -1686,6 +1625,7 @@ __device__ int encode_sequences(LDSA Lds& L, const Bytes& att, const Bytes& tmp,
 
 }  // namespace ze
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY
 // one wave per frame; block k of every frame: entropy coding, block decision, frame assembly
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_entropy_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level, int k,
@@ -1698,122 +1638,7 @@ lzh_zstd_entropy_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readabl
     const uint64_t ioff = f * chunk_size;
     if (ioff >= n_total && !(n_total == 0 && f == 0)) return;
     const uint64_t nf = n_total ? min(chunk_size, n_total - ioff) : 0;
-    const ZParams P = params_for(level, nf);
-    if (!P.ok) return;
-    const uint64_t nblocks = nf ? (nf + P.bsize - 1) / P.bsize : 1;
-    if ((uint64_t)k >= nblocks) return;
-    uint8_t* fs = scratch + f * fstride;
-    rsrc_t hdr = make_rsrc(fs, 1024);
-    Bytes out;
-    out.init(stage + f * stride, stride);
-    int out_off;
-    if (k == 0) {
-        // ZSTD_writeFrameHeader (zstd_compress.c:4012-4058): single segment, content size, no checksum
-        const uint64_t wsize = 1ull << P.wlog;
-        const int single = wsize >= nf;
-        const int fcs = (nf >= 256) + (nf >= 65536 + 256) + (nf >= 0xFFFFFFFFull);
-        int o = 0;
-        if (lane == 0) {
-            out.st8(0, 0x28); out.st8(1, 0xB5); out.st8(2, 0x2F); out.st8(3, 0xFD);
-            out.st8(4, (uint32_t)((single << 5) + (fcs << 6)));
-        }
-        o = 5;
-        if (!single) { if (lane == 0) out.st8(o, (P.wlog - 10) << 3); o++; }
-        if (lane == 0) {
-            if (fcs == 0) { if (single) out.st8(o, (uint32_t)nf & 0xff); }
-            else if (fcs == 1) { const uint32_t v = (uint32_t)(nf - 256); out.st8(o, v & 0xff); out.st8(o + 1, v >> 8); }
-            else if (fcs == 2) { for (int i = 0; i < 4; i++) out.st8(o + i, (uint32_t)(nf >> (8 * i)) & 0xff); }
-            else { for (int i = 0; i < 8; i++) out.st8(o + i, (uint32_t)(nf >> (8 * i)) & 0xff); }
-        }
-        o += fcs == 0 ? (single ? 1 : 0) : (fcs == 1 ? 2 : (fcs == 2 ? 4 : 8));
-        out_off = o;
-        if (lane == 0) { st_b32(hdr, 16, 1u); st_b32(hdr, 20, 4u); st_b32(hdr, 24, 0u); }
-    } else {
-        out_off = (int)uni(ld_b32(hdr, 28));
-    }
-    if (nf == 0) {                                        // ZSTD_writeEpilogue: empty last raw block
-        if (lane == 0) { out.st8(out_off, 1); out.st8(out_off + 1, 0); out.st8(out_off + 2, 0); csizes[f] = (uint32_t)out_off + 3; }
-        return;
-    }
-    const int bs = k * (int)P.bsize;
-    const int be = (int)min<uint64_t>(nf, (uint64_t)bs + P.bsize);
-    const int len = be - bs;
-    const int last = (uint64_t)be == nf;
-    Bytes in_b;
-    in_b.init(in + ioff, min<uint64_t>(in_readable - ioff, nf + 16));
-    const int skip = len < 7 || uni(ld_b32(hdr, 32)) != 0u;
-    int csize = 0, newTable = 0;
-    Bytes att;
-    att.init(fs + att_off, tmp_off - att_off);
-    if (!skip) {
-        const int ns = (int)uni(ld_b32(hdr, 0)), nl = (int)uni(ld_b32(hdr, 4));
-        const int prevRepeat = (int)uni(ld_b32(hdr, 24));
-        if (prevRepeat) {
-            rsrc_t ht = make_rsrc(fs + zc::kHufOff, 768);
-            for (int s = lane; s < 256; s += 64) {
-                L.pnb[s] = (uint8_t)ld_u8(ht, s);
-                L.pval[s] = (uint16_t)(ld_u8(ht, 256 + 2 * s) | (ld_u8(ht, 257 + 2 * s) << 8));
-            }
-            wave_lds_fence();
-        }
-        Bytes lits, tmp;
-        lits.init(fs + lit_off, P.bsize + 64);
-        tmp.init(fs + tmp_off, P.bsize + 256);
-        int o = ze::compress_literals(L, att, tmp, lits, nl, ns, P, prevRepeat, newTable, lane);
-        if (lane == 0) {
-            if (ns < 128) att.st8(o, (uint32_t)ns);
-            else if (ns < 0x7F00) { att.st8(o, (uint32_t)((ns >> 8) + 0x80)); att.st8(o + 1, (uint32_t)ns & 0xff); }
-            else { att.st8(o, 0xFF); att.st8(o + 1, (uint32_t)(ns - 0x7F00) & 0xff); att.st8(o + 2, (uint32_t)(ns - 0x7F00) >> 8); }
-        }
-        o += ns < 128 ? 1 : (ns < 0x7F00 ? 2 : 3);
-        if (ns) {
-            const int sz = ze::encode_sequences(L, att, tmp, o, make_rsrc(fs + seq_off, (uint32_t)(lit_off - seq_off)), ns, lane);
-            csize = sz ? o + sz : 0;
-        } else {
-            csize = o;
-        }
-        if (csize && csize >= len - ((len >> 6) + 2)) csize = 0;   // ZSTD_minGain
-    }
-    if (len >= 7 && k > 0 && csize < 25) {                          // RLE block (not for the first block)
-        const uint32_t b0 = in_b.b(bs);
-        bool diff = false;
-        for (int i = lane; i < len; i += 64) diff |= in_b.b(bs + i) != b0;
-        if (!ballot(diff)) csize = 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int bsz;
-    if (csize == 0) {
-        if (lane == 0) { const uint32_t h = (uint32_t)last + ((uint32_t)len << 3); out.st8(out_off, h & 0xff); out.st8(out_off + 1, (h >> 8) & 0xff); out.st8(out_off + 2, h >> 16); }
-        copy_span(in_b, bs, out, out_off + 3, len, lane, 64);
-        bsz = 3 + len;
-    } else if (csize == 1) {
-        if (lane == 0) {
-            const uint32_t h = (uint32_t)last + (1u << 1) + ((uint32_t)len << 3);
-            out.st8(out_off, h & 0xff); out.st8(out_off + 1, (h >> 8) & 0xff); out.st8(out_off + 2, h >> 16);
-            out.st8(out_off + 3, in_b.b(bs));
-        }
-        bsz = 4;
-    } else {
-        if (lane == 0) { const uint32_t h = (uint32_t)last + (2u << 1) + ((uint32_t)csize << 3); out.st8(out_off, h & 0xff); out.st8(out_off + 1, (h >> 8) & 0xff); out.st8(out_off + 2, h >> 16); }
-        copy_span(att, 0, out, out_off + 3, csize, lane, 64);
-        bsz = 3 + csize;
-        // confirm repcodes and the Huffman table (ZSTD_blockState_confirmRepcodesAndEntropyTables)
-        if (lane == 0) { st_b32(hdr, 16, ld_b32(hdr, 8)); st_b32(hdr, 20, ld_b32(hdr, 12)); }
-        if (newTable) {
-            rsrc_t ht = make_rsrc(fs + zc::kHufOff, 768);
-            for (int s = lane; s < 256; s += 64) {
-                st_u8(ht, s, L.nb[s]);
-                st_u8(ht, 256 + 2 * s, L.val[s] & 0xff);
-                st_u8(ht, 257 + 2 * s, L.val[s] >> 8);
-            }
-            if (lane == 0) st_b32(hdr, 24, 1u);
-        }
-    }
-    out_off += bsz;
-    if (lane == 0) {
-        st_b32(hdr, 28, (uint32_t)out_off);
-        if (last) csizes[f] = (uint32_t)out_off;
-    }
+#include "zstdc_entropy_body.inc"
 }
 
 #include "launch.h"
@@ -1857,6 +1682,21 @@ extern "C" int lzh_debug_zstdc_split(int on) {
     return 0;
 }
 
+#ifndef LZH_ZSTD_LDS_MAX
+#define LZH_ZSTD_LDS_MAX 65536u   // largest hash table kept in LDS (else in the frame's scratch, via L2)
+#endif
+// the match kernels' dynamic LDS for frames of up to chunk_size bytes: the hash table of that size's parameters
+// (0: it lives in the frame's scratch); the kernels pick the table kind from chunk_size and this
+uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size) {
+    const ZParams PF = params_for(level, chunk_size);
+    // 3-byte entries (LdsTab24) below 16 MiB chunks, else 4-byte ones
+    // (17-bit entries, LdsTab17, for chunks of at most 128 KiB)
+    const uint32_t ebytes = chunk_size < (16u << 20) ? 3u : 4u;
+    const uint32_t t17 = (2u << PF.hlog) + std::max((1u << PF.hlog) / 8u, 4u);
+    return (4u << PF.hlog) > (uint32_t)LZH_ZSTD_LDS_MAX ? 0u
+           : (LZH_ZSTD_TAB17 && chunk_size <= 131072u) ? ((t17 + 15u) & ~15u) : (ebytes << PF.hlog);
+}
+
 hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                                     int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
                                     uint8_t* scratch, hipStream_t s) {
@@ -1867,15 +1707,7 @@ hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_
     const size_t fstride = lzh_zstd_scratch_stride(chunk_size, level);
     const Layout Lo = layout_for(PF.bsize, 16);   // offsets below tab_off do not depend on hlog
     const uint32_t nblocks = (uint32_t)((std::min<uint64_t>(chunk_size, std::max<uint64_t>(n_total, 1)) + PF.bsize - 1) / PF.bsize);
-#ifndef LZH_ZSTD_LDS_MAX
-#define LZH_ZSTD_LDS_MAX 65536u   // largest hash table kept in LDS (else in the frame's scratch, via L2)
-#endif
-    // 3-byte entries (LdsTab24) below 16 MiB chunks, else 4-byte ones
-    // (17-bit entries, LdsTab17, for chunks of at most 128 KiB)
-    const uint32_t ebytes = chunk_size < (16u << 20) ? 3u : 4u;
-    const uint32_t t17 = (2u << PF.hlog) + std::max((1u << PF.hlog) / 8u, 4u);
-    const uint32_t lds_tab = (4u << PF.hlog) > (uint32_t)LZH_ZSTD_LDS_MAX ? 0u
-                             : (LZH_ZSTD_TAB17 && chunk_size <= 131072u) ? ((t17 + 15u) & ~15u) : (ebytes << PF.hlog);
+    const uint32_t lds_tab = lzh_zstd_lds_table(level, chunk_size);
     auto match = [&](hipStream_t st, uint32_t k, uint32_t f0, uint32_t nf) {
         hipLaunchKernelGGL(lzh_zstd_match_kernel, dim3(nf), dim3(64), lds_tab, st, in, n_total, in_readable,
                            chunk_size, level, (int)k, scratch, (uint64_t)fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off,
@@ -1910,3 +1742,4 @@ hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_
     }
     return hipGetLastError();
 }
+#endif   // LZH_DEVICE_FUNCTIONS_ONLY
