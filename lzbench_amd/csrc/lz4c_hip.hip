@@ -226,41 +226,9 @@ __device__ __forceinline__ int wave_incl_scan(int x) {
     return x;
 }
 
-#ifndef LZH_LZ4_DPPEND
-#define LZH_LZ4_DPPEND 1
-#endif
-#ifndef LZH_LZ4_RESTORE2
-#define LZH_LZ4_RESTORE2 1
-#endif
-#ifndef LZH_LZ4_RW   // the parse kernel without its LDS input ring: register-window P sides, 10 waves per CU
-#define LZH_LZ4_RW 1
-#endif
-#ifndef LZH_LZ4_WALK4   // the chain walk with one register (4 instructions a member instead of 6)
-#define LZH_LZ4_WALK4 1
-#endif
-#ifndef LZH_LZ4_MASKS   // the resolve's probed / inserted sets as lane masks (no VGPR round trips)
-#define LZH_LZ4_MASKS 1
-#endif
-#ifndef LZH_LZ4_PADLDS
-#define LZH_LZ4_PADLDS 0
-#endif
-#ifndef LZH_LZ4_EXPECT   // run batches as the likely branch (block frequencies for the register allocator; the run
-                         // batch's state updates as selects instead were 1-2 % slower, profiles/r06_o)
-#define LZH_LZ4_EXPECT 1
-#endif
-#define RUNB_LIKELY(x) (LZH_LZ4_EXPECT ? __builtin_expect((x) != 0, 1) : (x) != 0)
-#ifndef LZH_LZ4_RUNB_SGPR   // the run / stride flag without a readfirstlane at the batch loop's head
-#define LZH_LZ4_RUNB_SGPR 1
-#endif
-#ifndef LZH_LZ4_SWP   // the switch to stride batches at the next batch's head (not on the run batches' back edge)
-#define LZH_LZ4_SWP 1
-#endif
-#ifndef LZH_LZ4_PRFRESH   // the stride path writes the deferred record fields too (no back-edge VGPR copies)
-#define LZH_LZ4_PRFRESH 1
-#endif
-#ifndef LZH_LZ4_AMASK   // the resolve's hit set A as a uniform mask built from single-compare ballots
-#define LZH_LZ4_AMASK 1
-#endif
+// run batches as the likely branch (block frequencies for the register allocator; the run batch's state updates as
+// selects instead were 1-2 % slower, profiles/r06_o)
+#define RUNB_LIKELY(x) __builtin_expect((x) != 0, 1)
 
 // Sequences found by one batch, one per member lane (the lane of the sequence's match start):
 // anchor, literal count, offset, match length - 4, first output byte within the batch's
@@ -651,9 +619,10 @@ struct LinkCtl {
 // e+1, e+2, then steps of acc for 64 probes: offsets {0, 1, 2, 2+acc, 2+2acc, ..} from e.  Run
 // batches cover the first 64 search probes of each segment (as with acc 1); later probes and the
 // chunk tail (where a probe's forwardIp could pass mflimit) go through stride batches.
-// kRW (records only): no LDS input ring -- the table alone (16 KiB) leaves room for 10 waves per CU instead of 9 --
-// and the run batches' P sides come from a register window of the input (see the loop top)
-template <bool kSmall, bool kStats, bool kRec = false, bool kFast = false, bool kLinked = false, bool kRW = false>
+// kRec (the records-only parse) has no LDS input ring -- the table alone (16 KiB) leaves room for 10 waves per CU
+// instead of 9 -- and its run batches' P sides come from a register window of the input (see the loop top); the
+// window serves only that parse: with in-kernel emission the literals are read from the ring
+template <bool kSmall, bool kStats, bool kRec = false, bool kFast = false, bool kLinked = false>
 __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc, LDSA uint32_t* tab,
                                LDSA uint32_t* ringw, LDSA uint8_t* outb, uint32_t* out_size,
                                unsigned long long* stats, rsrc_t recs, uint32_t* rec_hdr, LinkCtl* lk = nullptr) {
@@ -680,10 +649,9 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
 #pragma unroll
         for (int i = 0; i < 16; i++) lds_zero16(t4 + 4 * (i * LZH_WAVE + lane));
     }
-    static_assert(!kRW || kRec, "the register window serves the records-only parse");
-    // (without the ring and with every P side from memory -- 10 waves -- 6 % slower, profiles/r05_lnr; kRW keeps
-    // the P sides off memory's latency with a register window)
-    constexpr bool kRingOn = !kRW;
+    // (without the ring and with every P side from memory -- 10 waves -- 6 % slower, profiles/r05_lnr; the register
+    // window keeps the P sides off memory's latency)
+    constexpr bool kRingOn = !kRec;
     Ring R{ringw, in.sh, 0, 0, kRingOn, kRec};   // (the parse kernel's ring carries a 32-byte mirror)
     if (kLinked) R.fill = max(((b0 + in.sh) & ~255) - 256, 0);   // (a block's ring starts just before it)
     OutRing O{outb, out.sh, 0};
@@ -721,7 +689,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
         // pins = a pending ip-2 table fill (lz4.c:1145-1146) sitting at base.  Stride batches
         // (any other schedule): one sequence per batch, the search from s with k0 probes done.
         // (ints: uniform SGPR phis, not lane masks; runb 2 = a run batch's 64 probes found nothing, stride batches
-        // from the next batch's head on, LZH_LZ4_SWP)
+        // from the next batch's head on)
         int runb = kFast || acc == 1, retest = 0, go = 1;
         const int dlim = kFast ? 2 + 62 * acc : 64;      // last run-batch probe: segment origin + dlim
         int base = b0 + 1, q = b0 + 1, qlim = b0 + dlim, pins = -1;
@@ -735,7 +703,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
             PAT = 3ull | (PER << 2);
         }
 
-        // (kRW) register window over the input, one dword a lane: Wc = the 256 bytes at descriptor offset WX (a
+        // (kRec) register window over the input, one dword a lane: Wc = the 256 bytes at descriptor offset WX (a
         // multiple of 4), Wn = those at WX + 128.  A run batch at base takes its P sides from Wc when its 64
         // positions' bytes lie in it (0 <= base + sh - WX <= kWinMax), else moves the window up by 128 (Wc = Wn)
         // when that covers it, else reads them from memory and restarts the window at its base (2.8 batches per
@@ -753,14 +721,13 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
             if (!go || (kLinked && aborted) || guard >= 4 * n + 64) break;
             // (runb: no readfirstlane -- its phi is uniform from constants under uniform branches, and the
             // readfirstlane kept it in a VGPR: a v_mov + v_readfirstlane a batch)
-            if (!LZH_LZ4_RUNB_SGPR) runb = unii(runb);
             retest = unii(retest);
             base = unii(base); q = unii(q); qlim = unii(qlim); pins = unii(pins); s = unii(s); k0 = unii(k0);
             op = unii(op); anchor = unii(anchor); rc_tot = unii(rc_tot); nrec = unii(nrec);
             R.fill = unii(R.fill); R.ready = unii(R.ready); O.flushed = unii(O.flushed);
             so = unii(so);
             LZ_STAT(0, 1);
-            if (LZH_LZ4_SWP && runb == 2) {   // a run batch's 64 probes found nothing: stride batches from here
+            if (runb == 2) {   // a run batch's 64 probes found nothing: stride batches from here
                 runb = 0;
                 s = so + 1;
                 k0 = LZH_WAVE;
@@ -821,7 +788,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
             // ---- P-side bytes (ring when it covers the batch), hash, table read / claim / read back
             PSide ps;
             uint32_t b4 = 0;
-            if (kRW) {
+            if (kRec) {
                 WX = unii(WX); wc_ok = unii(wc_ok); wn_ok = unii(wn_ok);
                 int o = front + in.sh - WX;
                 // 1: Wc, 2: the window moved up 128 (scalar ints and unsigned range tests: no lane-mask booleans)
@@ -907,10 +874,13 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                 lep = l;
                 const uint32_t y = ps.m4 ^ gm4;
                 bep = y ? (int)((uint32_t)__builtin_clz(y) >> 3) : 4;
+                // (okp is never read -- the resolve works on OKP -- but without this short-circuit the compiler emits
+                // different code for the block, see DESIGN.md "Retired switches")
                 okp = valid && gw == ps.w;
+                (void)okp;
                 OKP = ballot(gw == ps.w) & vmask;
             }
-            if (kRW) {
+            if (kRec) {
                 // the window's next part, after the candidate loads (no explicit wait: the compiler waits for the
                 // candidate data by register, which leaves this load in flight)
                 Wn = ld_b32(in.r, WX + 128 + 4 * lane);
@@ -935,13 +905,12 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
             bool eqw;
             bool ok = eval_lane(ps, W, valid, bkr, len, &eqw);
             if (!kSmall) ok = ok && (cand + 65535u >= (uint32_t)p);
-            // (LZH_LZ4_AMASK: `ok` as a lane mask, balloted next to its compares -- an i1 that crosses a block
-            // boundary goes through a VGPR to be balloted)
+            // (`ok` as a lane mask, balloted next to its compares -- an i1 that crosses a block boundary goes
+            // through a VGPR to be balloted; the zero initialiser is dead, but without it the compiler emits
+            // different code for the loop, see DESIGN.md "Retired switches")
             uint64_t OKM = 0;
-            if (LZH_LZ4_AMASK) {
-                OKM = ballot(eqw) & vmask;
-                if (!kSmall) OKM &= ballot(cand + 65535u >= (uint32_t)p);
-            }
+            OKM = ballot(eqw) & vmask;
+            if (!kSmall) OKM &= ballot(cand + 65535u >= (uint32_t)p);
 
             if (RUNB_LIKELY(runb)) {
                 // ================= run batch: resolve every sequence that starts in the batch
@@ -971,9 +940,8 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                 // check the assumption against the resolved inserted set; repeat with corrected
                 // candidates until consistent (each round fixes a prefix of the batch).
                 int ak = prev;
-                bool oke = prev >= 0 ? okp : ok;
-                // (LZH_LZ4_AMASK) the lanes whose candidate matches, carried as a uniform mask: a ballot of the
-                // merged bool `oke` costs a VGPR round trip per round, the mask costs three scalar operations
+                // the lanes whose candidate matches, carried as a uniform mask: a ballot of a merged per-lane bool
+                // costs a VGPR round trip per round, the mask costs three scalar operations
                 const uint64_t Am0 = (coll & OKP) | (OKM & ~coll);
                 uint64_t Am = Am0;
                 uint32_t ce = prev >= 0 ? (uint32_t)(base + prev) : cand;
@@ -983,10 +951,10 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                 int eL = 0;                                            // end lane of the last member
                 bool endp = false;                                     // the parse ends in this batch
                 for (int round = 0; round <= LZH_WAVE; round++) {
-                    const uint64_t A = LZH_LZ4_AMASK ? uni64(Am) : ballot(oke);
+                    const uint64_t A = uni64(Am);
                     // if lane l starts a sequence: match count, end lane, next hit at or after the end
                     cn = min(le, mlimit - (p + kMinMatch));
-                    const bool lng = (LZH_LZ4_AMASK ? lane_on(A) : oke) && le == 20 && p + kMinMatch + 20 < mlimit;
+                    const bool lng = lane_on(A) && le == 20 && p + kMinMatch + 20 < mlimit;
                     e = lane + kMinMatch + cn;
                     int f = ctz64v(e < LZH_WAVE ? (A & (PAT << e)) : 0ull);
                     // chain walk (lz4.c:1142-1200: match end -> re-test -> search from ip+1)
@@ -1005,25 +973,15 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                         LZ_CLK(10);                            // (stats: per-lane links)
                         // (links strictly increase, so the walks end)
                         for (;;) {
-                            int fs;
-                            if (LZH_LZ4_WALK4) {
-                                // common case: plain links, one register for the walk (the last member is the
-                                // highest bit of Mm afterwards: members increase) -- 4 instructions a member
-                                fs = unii(sl);
-                                Mm = uni64(Mm);   // (uniform already: readfirstlane keeps every instantiation in SGPRs)
-                                do {
-                                    asm("s_bitset1_b64 %0, %1" : "+s"(Mm) : "s"(fs));
-                                    fs = rdlanei(link, fs);
-                                } while (fs < LZH_WAVE);
-                                sl = 63 - __builtin_clzll(Mm);
-                            } else {
-                            for (;;) {                                 // common case: plain links
-                                Mm |= 1ull << sl;
-                                fs = rdlanei(link, sl);
-                                if (fs >= LZH_WAVE) break;
-                                sl = fs;
-                            }
-                            }
+                            // common case: plain links, one register for the walk (the last member is the
+                            // highest bit of Mm afterwards: members increase) -- 4 instructions a member
+                            int fs = unii(sl);
+                            Mm = uni64(Mm);   // (uniform already: readfirstlane keeps every instantiation in SGPRs)
+                            do {
+                                asm("s_bitset1_b64 %0, %1" : "+s"(Mm) : "s"(fs));
+                                fs = rdlanei(link, fs);
+                            } while (fs < LZH_WAVE);
+                            sl = 63 - __builtin_clzll(Mm);
                             if (fs != 0x80) break;                     // the chain leaves the batch
                             int es;
                             if (rdlane((uint32_t)lng, sl)) {           // match runs past the window
@@ -1043,35 +1001,27 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                         eL = rdlanei(e, sl);
                         LZ_CLK(11);                            // (stats: the scalar walk)
                         // lanes strictly inside a member's match are not probed; ip-2 is inserted
-                        if (!kFast && LZH_LZ4_DPPEND) {
+                        if (!kFast) {
                             // the end of the last member at or before each lane: members' ends increase along
                             // the chain (the next member starts at or after the previous end), so it is the
                             // running max of the members' ends -- DPP, no LDS round trip
                             const bool mem = lane_on(Mm);
                             const int ej = wave_incl_max(mem ? e : 0);
-                            if (LZH_LZ4_MASKS) {
-                                // (as lane masks: one compare each, the rest scalar -- a ballot of a compound
-                                // condition goes through a VGPR and back)
-                                const uint64_t inside = ballot(lane < ej) & ~Mm;
-                                const uint64_t below_eL = endip && eL < LZH_WAVE ? (1ull << eL) - 1ull : ~0ull;
-                                E = (~0ull << lo) & ~inside & below_eL;
-                                I = ballot(lane + 2 == ej) & ~Mm;      // lz4.c:1146 (a member's own end is >= lane + 4)
-                            } else {
-                            const bool inside = !mem && lane < ej;
-                            E = ballot(lane >= lo && !inside && (!endip || lane < eL));
-                            I = ballot(!mem && lane == ej - 2);        // lz4.c:1146 (a member's own end is >= lane + 4)
-                            }
+                            // (as lane masks: one compare each, the rest scalar -- a ballot of a compound
+                            // condition goes through a VGPR and back)
+                            const uint64_t inside = ballot(lane < ej) & ~Mm;
+                            const uint64_t below_eL = endip && eL < LZH_WAVE ? (1ull << eL) - 1ull : ~0ull;
+                            E = (~0ull << lo) & ~inside & below_eL;
+                            I = ballot(lane + 2 == ej) & ~Mm;          // lz4.c:1146 (a member's own end is >= lane + 4)
                         } else {
-                        const uint64_t mle = Mm & (below | (1ull << lane));
-                        const int j = mle ? 63 - __builtin_clzll(mle) : lane;
-                        const int ej = (int)lane_gather((uint32_t)e, j);
-                        const bool inside = mle && lane > j && lane < ej;
-                        bool probed = lane >= lo && !inside;
-                        if (kFast)   // before the first member: the first segment's pattern; after a
-                            probed = mle ? (lane == j || (lane >= ej && ((PAT >> ((lane - ej) & 63)) & 1ull)))
-                                         : lane_on(P0);        // member's end: its pattern
-                        E = ballot(probed && (!endip || lane < eL));
-                        I = ballot(mle && lane == ej - 2);             // lz4.c:1146
+                            // before the first member: the first segment's pattern; after a member's end: its pattern
+                            const uint64_t mle = Mm & (below | (1ull << lane));
+                            const int j = mle ? 63 - __builtin_clzll(mle) : lane;
+                            const int ej = (int)lane_gather((uint32_t)e, j);
+                            const bool probed = mle ? (lane == j || (lane >= ej && ((PAT >> ((lane - ej) & 63)) & 1ull)))
+                                                    : lane_on(P0);
+                            E = ballot(probed && (!endip || lane < eL));
+                            I = ballot(mle && lane == ej - 2);         // lz4.c:1146
                         }
                         endp = endip || (eL < LZH_WAVE && LZH_WAVE - 1 >= fv);   // or the search ran past mflimit
                     }
@@ -1084,13 +1034,10 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                     if (!FX) break;
                     LZ_STAT(2, 1);
                     const bool far = fix && kt >= 0 && kt != prev;
-                    if (LZH_LZ4_AMASK) {
-                        const uint64_t KN = ballot(kt < 0);
-                        Am = (Am & ~FX) | (FX & ((KN & OKM) | (~KN & OKP)));
-                    }
+                    const uint64_t KN = ballot(kt < 0);
+                    Am = (Am & ~FX) | (FX & ((KN & OKM) | (~KN & OKP)));
                     if (fix) {
                         ak = kt;
-                        if (!LZH_LZ4_AMASK) oke = kt < 0 ? ok : okp;
                         ce = kt < 0 ? cand : (uint32_t)(base + kt);
                         be = kt < 0 ? bkr : bep;
                         le = kt < 0 ? len : lep;
@@ -1109,9 +1056,8 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                             le = l;
                             const uint32_t y = ps.m4 ^ gm4;
                             be = y ? (int)((uint32_t)__builtin_clz(y) >> 3) : 4;
-                            if (!LZH_LZ4_AMASK) oke = valid && gw == ps.w;
                         }
-                        if (LZH_LZ4_AMASK) Am = (Am & ~FR) | (FR & ballot(gw == ps.w) & vmask);
+                        Am = (Am & ~FR) | (FR & ballot(gw == ps.w) & vmask);
                     }
                 }
                 LZ_CLK(5);                                             // chain resolve
@@ -1146,7 +1092,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                 } else {
                     // table: the last inserted lane of each slot, or the slot's old value
                     const bool inI = lane_on(I);
-                    if (LZH_LZ4_RESTORE2 && !losers) {
+                    if (!losers) {
                         // (no two lanes share a slot: every claim stands, a lane not inserted puts its old value back)
                         if (valid && !inI) T.put(h, old);
                     } else if (vmask == ~0ull) {
@@ -1154,8 +1100,6 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                         // the slot's last inserted lane, else its old value
                         const uint64_t gi = grp & I;
                         T.put(h, gi ? (uint32_t)(base + 63 - __builtin_clzll(gi)) : old);
-                    } else if (!losers) {
-                        if (valid && !inI) T.put(h, old);
                     } else {
                         const uint64_t gi = grp & I;
                         const bool wr = valid && (gi == 0 || (inI && (gi & ~((2ull << lane) - 1ull)) == 0));
@@ -1185,14 +1129,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                     pins = -1;
                 }
                 if (swc) {
-                    if (LZH_LZ4_SWP) {
-                        runb = 2;   // (the switch itself at the next batch's head: off the run batches' back edge)
-                    } else {
-                        runb = 0;
-                        s = so + 1;
-                        k0 = LZH_WAVE;
-                        retest = 0;
-                    }
+                    runb = 2;   // (the switch itself at the next batch's head: off the run batches' back edge)
                 } else {
                     base = pins >= 0 ? pins : q;
                 }
@@ -1204,7 +1141,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
             // ================= stride batch: first sequence only
             // (the run path's deferred record fields are consumed by now: fresh values here too, so the batch loop's
             // back edge needs no VGPR copies to merge the run and stride paths' values)
-            if (LZH_LZ4_PRFRESH) { pr_e = 0; pr_cn = 0; pr_be = 0; pr_ce = 0; }
+            pr_e = 0; pr_cn = 0; pr_be = 0; pr_ce = 0;
             uint64_t hits = ballot(ok);
             const uint64_t tmask = ballot(!valid);
             const int fi = ffs64(tmask);
@@ -1371,11 +1308,11 @@ lzh_lz4_compress_stats_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_r
     LDSA uint32_t* ring = tab + 4096;
     const rsrc_t nr = make_rsrc(nullptr, 0);
     if (n < 65547) {
-        if (acc > 1) lz4v3::compress_chunk<true, true, true, true, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
-        else lz4v3::compress_chunk<true, true, true, false, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
+        if (acc > 1) lz4v3::compress_chunk<true, true, true, true>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
+        else lz4v3::compress_chunk<true, true, true, false>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
     } else {
-        if (acc > 1) lz4v3::compress_chunk<false, true, true, true, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
-        else lz4v3::compress_chunk<false, true, true, false, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
+        if (acc > 1) lz4v3::compress_chunk<false, true, true, true>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
+        else lz4v3::compress_chunk<false, true, true, false>(rin, n, rout, acc, tab, ring, nullptr, nullptr, stats, nr, hdr);
     }
 }
 
@@ -1390,9 +1327,8 @@ lzh_lz4_compress_stats_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_r
 extern "C" __global__ void __launch_bounds__(64)
 lzh_lz4_parse_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
                      uint8_t* recs, uint64_t rec_stride, uint32_t* rec_hdr, uint64_t frame_size, uint32_t bpf) {
-    // table only (the P sides from a register window, compress_chunk's kRW)
-    // (LZH_LZ4_PADLDS: extra bytes of LDS per wave -- an occupancy experiment, 0 in builds)
-    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 + (LZH_LZ4_RW ? 0 : lz4v3::kRing / 4 + 8) + LZH_LZ4_PADLDS / 4];
+    // table only (the P sides from a register window, compress_chunk's kRec)
+    __shared__ __attribute__((aligned(16))) uint32_t lds[4096];
     const uint64_t chunk = blockIdx.x;
     uint64_t off;
     int n;

@@ -11,9 +11,9 @@
     const rsrc_t rr = make_rsrc(recs + chunk * rec_stride, (uint32_t)rec_stride);
     uint32_t* hdr = rec_hdr + 2 * chunk;
     if (n < 65547) {
-        if (acc > 1) lz4v3::compress_chunk<true, false, true, true, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
-        else lz4v3::compress_chunk<true, false, true, false, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
+        if (acc > 1) lz4v3::compress_chunk<true, false, true, true>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
+        else lz4v3::compress_chunk<true, false, true, false>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
     } else {
-        if (acc > 1) lz4v3::compress_chunk<false, false, true, true, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
-        else lz4v3::compress_chunk<false, false, true, false, false, LZH_LZ4_RW>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
+        if (acc > 1) lz4v3::compress_chunk<false, false, true, true>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
+        else lz4v3::compress_chunk<false, false, true, false>(rin, n, rout, acc, tab, ring, nullptr, nullptr, nullptr, rr, hdr);
     }

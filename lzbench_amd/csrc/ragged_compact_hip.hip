@@ -64,7 +64,7 @@ lzh_compact_slots_kernel(const uint64_t* in_bytes, uint64_t max_bytes, int codec
 extern "C" __global__ void __launch_bounds__(64)
 lzh_lz4_parse_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
                              uint8_t* recs, uint32_t* rec_hdr, const LzhCompactLayout L) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 + (LZH_LZ4_RW ? 0 : lz4v3::kRing / 4 + 8) + LZH_LZ4_PADLDS / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t lds[4096];   // table only
     const uint64_t chunk = blockIdx.x;
     const uint64_t off = 0;
     const uint8_t* in;
@@ -101,7 +101,7 @@ lzh_lz4_emit_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_parse_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, uint8_t* recs,
                                 uint32_t* rec_hdr, uint32_t frags, const LzhCompactLayout L) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[(1 << 13) + 256 + 8 + LZH_SN_PADLDS / 4];   // table | ring + mirror
+    __shared__ __attribute__((aligned(16))) uint32_t lds[(1 << 13) + 256 + 8];   // table | ring + mirror
     const uint64_t chunk = blockIdx.x / frags;
     const uint32_t f = blockIdx.x - (uint32_t)chunk * frags;
     const uint64_t off = 0;

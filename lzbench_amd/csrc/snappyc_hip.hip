@@ -25,21 +25,6 @@
 namespace snv2 {
 
 #define SN_STAT(i, v) do { if (stats && lane == 0) atomicAdd(&stats[i], (unsigned long long)(v)); } while (0)
-#ifndef LZH_SN_PADLDS
-#define LZH_SN_PADLDS 0
-#endif
-#ifndef LZH_SN_DPPEND   // the members' ends by a DPP running max (no lane_gather round trips)
-#define LZH_SN_DPPEND 1
-#endif
-#ifndef LZH_SN_AMASK   // the resolve's hit set and probed set as uniform masks from single-compare ballots
-#define LZH_SN_AMASK 1
-#endif
-#ifndef LZH_SN_SHR   // the next hit after a copy from A shifted down by the copy's end (no per-lane pattern)
-#define LZH_SN_SHR 1
-#endif
-#ifndef LZH_SN_RESTORE2   // the table restore of a batch without slot collisions: no per-lane last-insert search
-#define LZH_SN_RESTORE2 1
-#endif
 // phase clocks of the run batches (experiment builds with -DLZH_SN_CLK; tools/sn_clk.py): the time since the
 // previous mark is charged to phase i, flushed per fragment into lzh_sn_clk_buf
 #ifdef LZH_SN_CLK
@@ -510,25 +495,28 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                 // resolve (as the LZ4 kernel): assume each collider's candidate is its closest
                 // earlier slot member, walk, verify against the inserted set, repeat if needed
                 int ak = prev;
-                bool oke = prev >= 0 ? okp : ok;
-                // (LZH_SN_AMASK) oke as a uniform mask: a ballot of the merged bool goes through a VGPR each round
+                // the lanes whose candidate matches, as a uniform mask: a ballot of a merged per-lane bool goes
+                // through a VGPR each round
+                // (the merged bool itself is never read, but without this select the compiler emits different code
+                // for the loop, see DESIGN.md "Retired switches")
+                const bool oke = prev >= 0 ? okp : ok;
+                (void)oke;
                 uint64_t Am = (coll & OKP) | (OKM & ~coll);
                 uint32_t ce = prev >= 0 ? (uint32_t)(base + prev) : cand;
                 int le = prev >= 0 ? lep : len;
                 uint64_t Mm = 0, I = I0;
                 int cn = 0, e = 0, eL = 0;
-                int ejm = 0;                                             // (LZH_SN_DPPEND: the last round's running max)
+                int ejm = 0;                                             // (the last round's running max of the members' ends)
                 bool endp = false;
                 for (int round = 0; round <= LZH_WAVE; round++) {
-                    const uint64_t A = LZH_SN_AMASK ? uni64(Am) : ballot(oke);
+                    const uint64_t A = uni64(Am);
                     cn = min(le, fn - (p + 4));                          // FindMatchLength limit (ip_end)
-                    const bool lng = (LZH_SN_AMASK ? lane_on(A) : oke) && le == 20 && p + 24 < fn;
+                    const bool lng = lane_on(A) && le == 20 && p + 24 < fn;
                     e = lane + 4 + cn;
-                    // next hit at or after e on the pattern after a copy (LZH_SN_SHR: A shifted down by e, one 64-bit
-                    // shift per lane, instead of the pattern built per lane)
+                    // next hit at or after e on the pattern after a copy (A shifted down by e, one 64-bit shift per
+                    // lane, instead of the pattern built per lane)
                     constexpr uint64_t kAft = 1ull | (kPat0 << 1);
-                    const int f = LZH_SN_SHR ? (e < LZH_WAVE ? e + ctz64v((A >> (e & 63)) & kAft) : LZH_WAVE)
-                                             : ctz64v(A & after_copy(e));
+                    const int f = e < LZH_WAVE ? e + ctz64v((A >> (e & 63)) & kAft) : LZH_WAVE;
                     const int link = (lng || p + 4 + cn >= ip_limit) ? 0x80 : f;
                     Mm = 0;
                     endp = false;
@@ -581,39 +569,20 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                         eL = rdlanei(e, sl);
                         // probed lanes: the initial plan up to the first member, then after each
                         // copy the re-test and the search pattern; ip-1 of each copy is inserted
-                        if (LZH_SN_DPPEND) {
-                            // end of the last member at or before the lane (0: none): members' ends
-                            // increase along the chain (after_copy(e) holds lanes >= e only)
-                            const bool mem = lane_on(Mm);
-                            ejm = wave_incl_max(mem ? e : 0);
-                            // (after_copy(ejm) at lane >= ejm is bit lane - ejm of kAfter: no per-lane 64-bit pattern)
-                            constexpr uint64_t kAfter = 1ull | (kPat0 << 1);
-                            if (LZH_SN_AMASK) {
-                                // members; lanes before the first member on the initial plan; lanes at or past the
-                                // last member's end on its pattern -- one compare per ballot, the rest scalar
-                                const uint64_t Z = ballot(ejm == 0), GE = ballot(lane >= ejm),
-                                               BT = ballot(((kAfter >> ((lane - ejm) & 63)) & 1ull) != 0ull);
-                                const uint64_t below_eL = endp && eL < LZH_WAVE ? (1ull << eL) - 1ull : ~0ull;
-                                E = (Mm | (Z & P0) | (~Z & GE & BT)) & below_eL;
-                            } else {
-                            bool pr;
-                            if (mem) pr = true;
-                            else if (ejm == 0) pr = lane_on(P0);
-                            else pr = lane >= ejm && ((kAfter >> ((lane - ejm) & 63)) & 1ull);
-                            E = ballot(pr && (!endp || lane < eL));
-                            }
-                            I = ballot(lane + 1 == ejm) & ~Mm;
-                        } else {
-                        const uint64_t mle = Mm & (below | (1ull << lane));
-                        const int j = mle ? 63 - __builtin_clzll(mle) : lane;
-                        const int ej = (int)lane_gather((uint32_t)e, j);
-                        bool pr;
-                        if (!mle) pr = lane_on(P0);
-                        else if (lane == j) pr = true;
-                        else pr = lane >= ej && ((after_copy(ej) >> lane) & 1ull);
-                        E = ballot(pr && (!endp || lane < eL));
-                        I = ballot(mle && lane != j && lane == ej - 1);
-                        }
+                        // end of the last member at or before the lane (0: none): members' ends increase along the
+                        // chain (after_copy(e) holds lanes >= e only), so it is their running max -- DPP, no
+                        // lane_gather round trips
+                        const bool mem = lane_on(Mm);
+                        ejm = wave_incl_max(mem ? e : 0);
+                        // (after_copy(ejm) at lane >= ejm is bit lane - ejm of kAfter: no per-lane 64-bit pattern)
+                        constexpr uint64_t kAfter = 1ull | (kPat0 << 1);
+                        // members; lanes before the first member on the initial plan; lanes at or past the last
+                        // member's end on its pattern -- one compare per ballot, the rest scalar
+                        const uint64_t Z = ballot(ejm == 0), GE = ballot(lane >= ejm),
+                                       BT = ballot(((kAfter >> ((lane - ejm) & 63)) & 1ull) != 0ull);
+                        const uint64_t below_eL = endp && eL < LZH_WAVE ? (1ull << eL) - 1ull : ~0ull;
+                        E = (Mm | (Z & P0) | (~Z & GE & BT)) & below_eL;
+                        I = ballot(lane + 1 == ejm) & ~Mm;
                     }
                     I = (Mm ? I : 0ull) | I0 | E;                          // (no stale bits from an earlier round)
                     if (!(coll & E)) break;
@@ -624,13 +593,10 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                     if (!FX) break;
                     SN_STAT(2, 1);
                     const bool far = fix && kt >= 0 && kt != prev;
-                    if (LZH_SN_AMASK) {
-                        const uint64_t KN = ballot(kt < 0);
-                        Am = (Am & ~FX) | (FX & ((KN & OKM) | (~KN & OKP)));
-                    }
+                    const uint64_t KN = ballot(kt < 0);
+                    Am = (Am & ~FX) | (FX & ((KN & OKM) | (~KN & OKP)));
                     if (fix) {
                         ak = kt;
-                        oke = kt < 0 ? ok : okp;
                         ce = kt < 0 ? cand : (uint32_t)(base + kt);
                         le = kt < 0 ? len : lep;
                     }
@@ -640,8 +606,8 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                         const uint32_t gw = lane_gather(ps.w, k);
                         const int lf = match_after4(ps, lane_gather(ps.q1, k), lane_gather(ps.q2, k),
                                                     lane_gather(ps.q3, k), lane_gather(ps.q4, k), lane_gather(ps.q5, k));
-                        if (far) { le = lf; oke = gw == ps.w; }
-                        if (LZH_SN_AMASK) Am = (Am & ~FR) | (FR & ballot(gw == ps.w));
+                        if (far) le = lf;
+                        Am = (Am & ~FR) | (FR & ballot(gw == ps.w));
                     }
                 }
                 SN_CLK(4);
@@ -649,16 +615,8 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                 if (Mm) {
                     SN_STAT(3, __builtin_popcountll(Mm));
                     const bool mem = lane_on(Mm);
-                    int anc;
-                    if (LZH_SN_DPPEND) {   // the previous member's end: the running max one lane down
-                        const int ep = wave_shr1(ejm);
-                        anc = ep > 0 ? base + ep : next_emit;
-                    } else {
-                    const uint64_t mb = Mm & below;
-                    const int jp = mb ? 63 - __builtin_clzll(mb) : lane;
-                    const int ep = (int)lane_gather((uint32_t)e, jp);
-                    anc = mb ? base + ep : next_emit;
-                    }
+                    const int ep = wave_shr1(ejm);   // the previous member's end: the running max one lane down
+                    const int anc = ep > 0 ? base + ep : next_emit;
                     const int lit = p - anc, mlen = 4 + cn;
                     const uint32_t offv = (uint32_t)(p - (int)ce);
                     rc_anc = (uint32_t)anc;
@@ -684,7 +642,7 @@ __device__ int compress_fragment(const Bytes& in, int fn, const Bytes& out, int 
                 SN_CLK(5);
                 if (endp) break;                                         // remainder from next_emit
                 // table: the last inserted lane of each slot, or the slot's old value
-                if (LZH_SN_RESTORE2 && !losers) {   // every lane owns its slot: inserted keeps p, else old
+                if (!losers) {   // every lane owns its slot: inserted keeps p, else old
                     T.put(h, lane_on(I) ? (uint32_t)p : old);
                     wave_lds_fence();
                 } else {   // every lane stores its slot's final value, all lanes of a slot agreeing (a run
@@ -997,8 +955,7 @@ constexpr int kFragRecs = 16384 + 32;
 extern "C" __global__ void __launch_bounds__(64)
 lzh_snappy_parse_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
                         uint8_t* recs, uint64_t rec_stride, uint32_t* rec_hdr, uint32_t frags) {
-    // (LZH_SN_PADLDS: extra bytes of LDS per wave -- an occupancy experiment, 0 in builds)
-    __shared__ __attribute__((aligned(16))) uint32_t lds[(1 << 13) + 256 + 8 + LZH_SN_PADLDS / 4];   // table | ring + mirror
+    __shared__ __attribute__((aligned(16))) uint32_t lds[(1 << 13) + 256 + 8];   // table | ring + mirror
     const uint64_t chunk = blockIdx.x / frags;
     const uint32_t f = blockIdx.x - (uint32_t)chunk * frags;
     const uint64_t off = chunk * chunk_size;
