@@ -252,15 +252,27 @@ int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t ma
  * a block attempt, a Huffman stream, the hash table), every one sized for max_chunk_bytes: nchunks x (the staging
  * stride + the scratch stride of max_chunk_bytes; 1.26 MiB a chunk at 128 KiB, 278 KiB at 16 KiB), so a skewed
  * batch pays for its largest chunk nchunks times.  There is no compact layout for zstd.  Decompress temp: the
- * scanned offsets (as 3b).
+ * scanned offsets (as 3b); the split decoder's temp below is optional.
  * lzh_zstd_ragged_max_packed_bytes: zstd expands small chunks (1..64 bytes become size + 9, which is not stored
  * raw); the bound is the sum of the per-chunk bounds lzh_stage_stride(LZH_CODEC_ZSTD, .) is sized for.
- * Decoding: every frame in the one-wave decoder of lzh_decompress_async (any frame of lzbench's shape, also with
- * the content checksum; the verdicts of that call); the four-kernel decoder does not take ragged batches yet.
- * Streams: every launch goes on hip_stream -- no side stream, event, host synchronisation or size read back (the
- * uniform zstd calls fork to side streams) -- so a captured call has no parallel branches. */
+ * Decoding: any frame of lzbench's shape, also with the content checksum; the verdicts of lzh_decompress_async.
+ * Which decoder runs follows that call's rule, by temp_bytes.  With lzh_zstd_ragged_decompress_temp_bytes every
+ * frame decodes in the one-wave decoder.  With at least lzh_zstd_ragged_decompress_split_temp_bytes, where that is
+ * not 0, the four-kernel split decoder runs (header, Huffman literals, sequences a frame per lane, execution) and
+ * the one-wave decoder takes only the frames it leaves: same statuses and bytes, several times faster on batches of
+ * many frames.  That answer is 0 for max_chunk_bytes below 16384 or above 16 MiB (no split decoder:
+ * pass the other size); otherwise it is the uniform decoder's layout for nchunks frames of max_chunk_bytes after the
+ * scanned offsets -- per frame the block, table and sequence-record areas (about 280 KiB a frame at 128 KiB), then
+ * frame states, frame fields and Huffman jobs -- so a skewed batch again pays for its largest chunk nchunks times.
+ * It is host arithmetic, non-decreasing in both arguments and never below the other answer; a temp_bytes between
+ * the two decodes one-wave.  A chunk whose device-side size passes max_chunk_bytes is left alone by both decoders
+ * (d_status[i] = -1), its temp slot included.
+ * Streams: every launch goes on hip_stream, with either temp -- no side stream, event, plan kernel, host
+ * synchronisation or size read back (the uniform zstd calls fork to side streams) -- so a captured call has no
+ * parallel branches. */
 size_t lzh_zstd_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks);
 size_t lzh_zstd_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_zstd_ragged_decompress_split_temp_bytes(size_t max_chunk_bytes, size_t nchunks);
 size_t lzh_zstd_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks);
 int lzh_zstd_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
                                    size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
@@ -270,6 +282,13 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
                                      const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
                                      size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
                                      size_t temp_bytes, void* hip_stream);
+/* Debug only, for tests (it may change with the temp layout): the regions of the split decoder's temp as byte
+ * ranges of d_temp, out[2 i], out[2 i + 1] = offset and size of region i: 0 scanned offsets, 1 per-frame areas
+ * (nchunks of out[14] bytes each), 2 the sequence waves' dummy words, 3 frame states (nchunks x i32: 2 = finished
+ * by the split kernels or not processed, 1 = handed to the one-wave decoder), 4 frame fields, 5 the Huffman jobs'
+ * counter, 6 the Huffman jobs; out[14] = a frame area's size, out[15] = the sizing answer (16 values).  Host
+ * arithmetic only; LZH_EARG where the sizing answer is 0 or out is null. */
+int lzh_debug_zstd_ragged_split_layout(size_t max_chunk_bytes, size_t nchunks, uint64_t* out);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

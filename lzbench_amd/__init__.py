@@ -102,6 +102,8 @@ SIGNATURES = {
     "lzh_zstd_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
     "lzh_zstd_ragged_decompress_temp_bytes": (_SZ, [_SZ, _SZ]),
     "lzh_zstd_ragged_max_packed_bytes": (_SZ, [_SZ, _SZ]),
+    "lzh_zstd_ragged_decompress_split_temp_bytes": (_SZ, [_SZ, _SZ]),
+    "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
     "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
@@ -388,11 +390,15 @@ class RaggedCodec:
     zstd / zstd_fast (the fast-strategy levels lzh_level_supported accepts for max_chunk_bytes) go through the
     lzh_zstd_*_ragged calls: one frame per chunk, a staging slot and a scratch area of the zstd kernels per chunk,
     each sized for max_chunk_bytes; compact=True raises ValueError (there is no compact layout for zstd).
+    split_decode=True (zstd only, else ValueError) sizes the decompress temp for the four-kernel split decoder
+    (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
+    batches); where there is none (max_chunk_bytes below 16 KiB) the temp stays the small one and every frame
+    decodes in the one-wave kernel, as with split_decode=False.
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
     def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
-                 max_total_bytes: Optional[int] = None, compact: bool = False):
+                 max_total_bytes: Optional[int] = None, compact: bool = False, split_decode: bool = False):
         import torch
         self.torch = torch
         self.codec = CODECS[codec]
@@ -404,9 +410,14 @@ class RaggedCodec:
         self.zstd = self.codec == LZH_CODEC_ZSTD
         if self.zstd and compact:
             raise ValueError("ragged batches: zstd has no compact layout")
+        if split_decode and not self.zstd:
+            raise ValueError("ragged batches: split_decode is a zstd option")
+        self.split_decode = split_decode
         if self.zstd:
             ct = L.lzh_zstd_ragged_compress_temp_bytes(self.level, max_chunk_bytes, max_chunks)
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
+            if split_decode:   # (0: no split decoder for chunks of this size)
+                dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
         elif compact:
             ct = L.lzh_ragged_compact_compress_temp_bytes(self.codec, self.max_total, max_chunk_bytes, max_chunks)
         else:

@@ -385,7 +385,8 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
 
 // ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
 // compress temp: chunk_temp(zstd) of nchunks staging slots and scratch areas sized for max_chunk_bytes;
-// decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors)
+// decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors), or
+// zstd_ragged_split_temp, with which the four-kernel split decoder runs
 
 static bool zstd_ragged_ok(int level, size_t max_chunk_bytes) {
     return max_chunk_bytes <= kLz4SplitMax && lzh_level_supported(LZH_CODEC_ZSTD, level, max_chunk_bytes) == 1;
@@ -403,6 +404,22 @@ size_t lzh_zstd_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, si
 
 size_t lzh_zstd_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks) {
     return max_chunk_bytes <= kLz4SplitMax ? ragged_decode_temp(nchunks).total : 0;
+}
+
+size_t lzh_zstd_ragged_decompress_split_temp_bytes(size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_ragged_split_temp(nchunks, max_chunk_bytes).total;
+}
+
+int lzh_debug_zstd_ragged_split_layout(size_t max_chunk_bytes, size_t nchunks, uint64_t* out) {
+    const ZstdRaggedSplitTemp t = zstd_ragged_split_temp(nchunks, max_chunk_bytes);
+    if (!t.ok || !out) return LZH_EARG;
+    const uint64_t v[14] = {t.scan,   (nchunks + 1) * sizeof(uint64_t), t.frames, t.frames_bytes, t.dummy, t.dummy_bytes,
+                            t.state,  t.state_bytes,                    t.fields, t.fields_bytes, t.njobs, 4,
+                            t.jobs,   t.jobs_bytes};
+    std::copy(v, v + 14, out);
+    out[14] = t.stride;
+    out[15] = t.total;
+    return LZH_OK;
 }
 
 size_t lzh_zstd_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks) {
@@ -452,6 +469,18 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
     if (!offs) {
         LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)((uint8_t*)d_temp + t.scan), nullptr, s));
         offs = (const uint64_t*)((uint8_t*)d_temp + t.scan);
+    }
+    // with room for it the split decoder's layout lives in temp (the offsets at the same place); with less every
+    // frame is decoded whole by one wave
+    const ZstdRaggedSplitTemp z = zstd_ragged_split_temp(nchunks, max_chunk_bytes);
+    uint8_t* base = (uint8_t*)d_temp;
+    if (z.ok && temp_bytes >= z.total) {
+        const LzhZstdSplitTemp split = {base + z.frames, (int32_t*)(base + z.state), base + z.fields,
+                                        (uint32_t*)(base + z.njobs), base + z.jobs};
+        LZH_CHECK(lzh_launch_zstd_decompress_ragged_split((const uint8_t*)d_packed, packed_readable, offs, d_csizes,
+                                                          d_out_ptrs, d_out_bytes, max_chunk_bytes, d_status,
+                                                          (uint32_t)nchunks, split, s));
+        return LZH_OK;
     }
     LZH_CHECK(lzh_launch_zstd_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
                                                 d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, s));

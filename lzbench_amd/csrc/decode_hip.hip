@@ -2028,7 +2028,10 @@ __device__ __forceinline__ int decode_frame(const Bytes& rin, const Bytes& lout,
 
 }  // namespace zstdd
 
-#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (the rest of the file: the split decoder, the kernels, the launchers)
+// (LZH_DEVICE_FUNCTIONS_ONLY 1, zstd_ragged_decode_hip.hip: the file ends here.  2, zstd_ragged_split_hip.hip: the
+// device functions of what follows as well -- the kernels and the launchers are left out, the kernels' bodies are
+// shared as text (zstdd_*_body.inc) or as a template (zstd_huf))
+#if !defined(LZH_DEVICE_FUNCTIONS_ONLY) || LZH_DEVICE_FUNCTIONS_ONLY >= 2
 // ---------------------------------------------------------------------------------------
 // zstd decoding in three kernels.  The sequence section's decoding chain (bit reader, three FSE
 // states, repcodes: ZSTD_decodeSequence, zstd_decompress_block.c:1169-1270) is serial within a
@@ -2424,8 +2427,22 @@ __device__ __forceinline__ int vsel(bool c, int a, int b) {
     return r;
 }
 
+// Where the literal kernel zstd_huf finds a frame's output.  Here the uniform geometry: frame i at byte
+// i * chunk_size of `out` (zstd_ragged_decode_hip.hip has the ragged one: per-chunk pointers).  slot(): the chunk
+// size the per-frame temp is laid out for; frames(): the frames of the call (the dummy area follows their temp);
+// at(): per lane, the output of a frame the header kernel accepted; idle(): what a lane without a stream points at.
+struct UniformOut {
+    uint64_t n_total, chunk_size;
+    uint8_t* out;
+    __device__ __forceinline__ uint64_t slot() const { return chunk_size; }
+    __device__ __forceinline__ uint64_t frames() const { return chunk_size ? (n_total + chunk_size - 1) / chunk_size : 0; }
+    __device__ __forceinline__ uint8_t* at(uint64_t frame) const { return out + frame * chunk_size; }
+    __device__ __forceinline__ uint8_t* idle() const { return out; }
+};
+
 }  // namespace zsplit
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (the sequence kernel knows no output geometry: ragged batches launch it as it is)
 // Sequences, one frame per lane (lanes 0 .. kFPW-1), in lock-step steps of one sequence per lane:
 // ZSTD_decodeSequence (zstd_decompress_block.c:1169-1270) with the FSE tables and the bit stream in
 // LDS, and every check of ZSTD_execSequence that depends on the output position (decode_block's).
@@ -2753,6 +2770,7 @@ lzh_zstd_seq_kernel(const uint8_t* packed, uint64_t packed_readable, const uint6
     if (LZH_ZSTD_STATS && stats && live && res == kLegacy) atomicAdd(&stats[6], 1ull);
     if (live) zfr[f].sv = res;   // (kGo, kLegacy or an error: lzh_zstd_exec_kernel applies it)
 }
+#endif   // LZH_DEVICE_FUNCTIONS_ONLY
 
 namespace zsplit {
 
@@ -2835,6 +2853,7 @@ __device__ __forceinline__ int exec_frame(const Bytes& rin, const Bytes& rout, c
 
 }  // namespace zsplit
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_hdr_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets, const uint32_t* csizes,
                     uint64_t n_total, uint64_t chunk_size, uint8_t* out, int32_t* status, uint8_t* zt, int32_t* zst,
@@ -2845,31 +2864,9 @@ lzh_zstd_hdr_kernel(const uint8_t* packed, uint64_t packed_readable, const uint6
     const uint64_t chunk = blockIdx.x;
     const uint64_t ooff = chunk * chunk_size;
     if (ooff >= n_total) return;
-    const int part = (int)min(chunk_size, n_total - ooff);
-    const uint64_t ioff = offsets[chunk];
-    const int cs = (int)csizes[chunk];
-    const uint64_t readable = ioff < packed_readable ? min<uint64_t>(packed_readable - ioff, (uint64_t)cs + 16) : 0;
-    Bytes rin, rout;
-    rin.init(packed + ioff, readable);
-    rout.init(out + ooff, (uint64_t)part);
-    if (cs == part) {                                  // stored raw by the chunk loop (lzbench.cpp:284-288)
-        copy_raw(rin, rout, part, lane);
-        if (lane == 0) {
-            status[chunk] = part;
-            zst[chunk] = zsplit::kDone;
-        }
-        return;
-    }
-    const zsplit::ZLayout Z = zsplit::zlayout(chunk_size);
-    zsplit::ZFrame fr{0, 0, -1, 0, 0, 0, 0, 0};
-    const int r = zsplit::hdr_frame(rin, rout, cs, L, part, zt + chunk * Z.stride, Z, fr, lane, stats, jobs, njobs,
-                                    (uint32_t)chunk);
-    if (lane == 0) {
-        if (r == zsplit::kGo) zfr[chunk] = fr;
-        zst[chunk] = r == zsplit::kGo ? zsplit::kGo : (r == zsplit::kLegacy ? zsplit::kLegacy : zsplit::kDone);
-        if (r < 0) status[chunk] = r;
-    }
+#include "zstdd_hdr_body.inc"
 }
+#endif
 
 // Huffman literal streams, one stream per lane: 4 sections a wave (lanes 4q + j: section q, stream
 // j), 8 waves per CU.  LDS: the sections' tables (2^11 cells each, rows of 16 lanes x 4 bytes as an
@@ -2895,11 +2892,12 @@ __host__ __device__ inline bool huf_par(int on, int nsym, uint32_t sz) {
 // trips: 8 sections a wave (36 KiB of LDS, one wave per SIMD) issue half the instructions per section of
 // 4 a wave (two waves per SIMD) -- 1 GiB -b128: mixed 5.3 -> 4.9 ms, text 2.0 -> 1.6 ms; 2 a wave 6.5 /
 // 3.2 ms -- but need 32 sections per CU to keep every SIMD busy, so launches with fewer frames keep 4.
-template <int HJ>
+// G: the output geometry (zsplit::UniformOut, or the ragged one)
+template <int HJ, class G>
 __device__ __forceinline__ void zstd_huf(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
-                                         uint64_t n_total, uint64_t chunk_size, uint8_t* out, int32_t* status,
-                                         uint8_t* zt, int32_t* zst, const zsplit::ZHuf* jobs, const uint32_t* njobs,
-                                         unsigned long long* stats, int par) {
+                                         const G& g, int32_t* status, uint8_t* zt, int32_t* zst,
+                                         const zsplit::ZHuf* jobs, const uint32_t* njobs, unsigned long long* stats,
+                                         int par) {
     using namespace zsplit;
     using namespace zstdd;
     constexpr int kHJ = HJ, kHL = 4 * kHJ;          // sections a wave, lanes in use
@@ -2919,7 +2917,7 @@ __device__ __forceinline__ void zstd_huf(const uint8_t* packed, uint64_t packed_
     }
     bool slive = jlive && zst[jf] == kGo && (uint32_t)j < jns &&
                  !huf_par(par, j == 3 ? (int)jlast : (int)jseg, jsz);   // (long streams: lzh_zstd_hufpar_kernel)
-    const ZLayout Z = zlayout(chunk_size);
+    const ZLayout Z = zlayout(g.slot());
     // resources from the wave's lowest frame: the packed streams and the table slots (per-lane 32-bit
     // offsets; a section whose offsets would not fit goes to the one-wave decoder)
     uint32_t fmin = jlive ? jf : 0xffffffffu;
@@ -2930,14 +2928,14 @@ __device__ __forceinline__ void zstd_huf(const uint8_t* packed, uint64_t packed_
     const rsrc_t rz = rsrc_over(zb0, (uint64_t)0xffffffffull);
     const uint64_t toff = (uint64_t)(jf - fmin) * Z.stride + Z.hufs() + (uint64_t)jtblk * kHufSlot;
     bool far_ = jlive && toff + kHufSlot > 0xffffffffull;
-    const uint64_t nfr = chunk_size ? (n_total + chunk_size - 1) / chunk_size : 0;
+    const uint64_t nfr = g.frames();
     uint8_t* const dummy = zt + nfr * Z.stride + (64ull * blockIdx.x) % zdummy_bytes(nfr);   // (spread like the seq kernel's)
     const int l4 = lane * 4;
     const int tl = (int)jtl;
     // this lane's stream
     int P = 0, lo = 0, nsym = 0, done = 0;
     int64_t A = 0;
-    uint8_t* dst = out;
+    uint8_t* dst = g.idle();
     if (slive) {
         const int64_t s0 = (int64_t)offsets[jf] + (int64_t)js0;
         A = s0 & ~3ll;
@@ -2946,7 +2944,7 @@ __device__ __forceinline__ void zstd_huf(const uint8_t* packed, uint64_t packed_
         lo = 8 * x0;
         P = 8 * X + hb32((uint32_t)packed[A + X]);   // (the end mark: checked non-zero by the header kernel)
         nsym = j == 3 ? (int)jlast : (int)jseg;
-        dst = out + (uint64_t)jf * chunk_size + jdst + (uint64_t)j * jseg;
+        dst = g.at(jf) + jdst + (uint64_t)j * jseg;
     }
     int hb0 = 0, hb1 = 0, rdy = 0, req = 0, iss = 0;
     {
@@ -3095,139 +3093,27 @@ __device__ __forceinline__ void zstd_huf(const uint8_t* packed, uint64_t packed_
 // the stream's bits after exactly nsym symbols (else the frame goes to the one-wave decoder (X2) or is
 // corrupt, as in lzh_zstd_huf_kernel).
 
+#ifndef LZH_DEVICE_FUNCTIONS_ONLY   // (the rest of the file: the uniform kernels, the launchers)
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_hufpar_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets, uint64_t chunk_size,
                        uint8_t* out, int32_t* status, uint8_t* zt, int32_t* zst, const zsplit::ZHuf* jobs,
                        const uint32_t* njobs, int par) {
-    using namespace zsplit;
-    using namespace zstdd;
-    __shared__ __attribute__((aligned(16))) uint32_t sbuf[kParCap / 4 + 128];   // dword d of the stream at d + 1
-    __shared__ __attribute__((aligned(16))) uint16_t tab[2048];
-    const int lane = threadIdx.x;
-    const uint32_t jid = blockIdx.x >> 2, j = blockIdx.x & 3u;
-    if (jid >= *njobs) return;
-    const ZHuf* J = jobs + jid;
-    const uint32_t jf = uni(J->frame), jns = uni(J->ns), jseg = uni(J->seg), jlast = uni(J->last);
-    if (j >= jns) return;
-    const int nsym = (int)(j == 3 ? jlast : jseg);
-    const uint32_t sz = uni(J->sz[j]);
-    if (!huf_par(par, nsym, sz) || uni((uint32_t)zst[jf]) != (uint32_t)kGo) return;
-    const ZLayout Z = zlayout(chunk_size);
-    const int tl = (int)uni(J->tl);
-    {   // the section's table (2^11 16-bit cells: symbol | nbBits << 8)
-        const uint32_t* tb = (const uint32_t*)(zt + (uint64_t)jf * Z.stride + Z.hufs() + (uint64_t)uni(J->tblk) * kHufSlot);
-        for (int i = lane; i < 1024; i += LZH_WAVE) ((LDSA uint32_t*)tab)[i] = tb[i];
-    }
-    // the stream's bytes [A, A + X] (A 4-aligned, the stream starting at byte x0), bits below its start zero
-    const int64_t s0 = (int64_t)offsets[jf] + (int64_t)uni(J->s0[j]);
-    const int64_t A = s0 & ~3ll;
-    const int x0 = (int)(s0 & 3), X = x0 + (int)sz - 1;
-    const int lo = 8 * x0;
-    const int nd = (X + 4) >> 2;
-    const int64_t avail = (int64_t)packed_readable - A;
-    const rsrc_t r = make_rsrc(packed + A, (uint32_t)max<int64_t>(0, min<int64_t>(avail, (int64_t)nd * 4)));
-    {
-        if (lane == 0) sbuf[0] = 0u;
-        // (LDS-DMA rows of 64 dwords, one wait; past nd the range check reads zeros)
-        for (int d0 = 0; d0 < nd + 2; d0 += LZH_WAVE)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(sbuf + 1 + d0), 4,
-                                                     4 * (d0 + lane), 0, 0, 0);
-    }
-    wait_vm();
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): table and stream in LDS
-    const uint32_t lastb = (sbuf[(X >> 2) + 1] >> (8 * (X & 3))) & 0xffu;
-    // bits [bq, bq + tl) (bq >= -32: the zero dword below the stream), zero below lo
-    auto bits = [&](int bq) -> uint32_t {
-        const int b = bq + 32, d = b >> 5;
-        const volatile LDSA uint32_t* s = (const volatile LDSA uint32_t*)sbuf;
-        uint32_t v = __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(s[d + 1], s[d], (uint32_t)b & 31u), 0u, (uint32_t)tl);
-        if (bq < lo) v &= lo - bq >= 32 ? 0u : (~0u << (lo - bq));
-        return v;
-    };
-    const int P0 = 8 * X + (lastb ? hb32(lastb) : 0);   // (the end mark: checked non-zero by the header kernel)
-    // this lane's share (P0 - lane * seg, P0 - (lane + 1) * seg], the last one down to lo
-    const int nbits = P0 - lo;
-    const int seg = (nbits + LZH_WAVE - 1) / LZH_WAVE;
-    const int top = P0 - lane * seg;
-    const int bot = lane == LZH_WAVE - 1 ? lo : max(P0 - (lane + 1) * seg, lo);
-    const int guard = seg + 64;
-    // decode the share from start: the chain's exit (the first symbol top at or below bot) and its symbols
-    auto pass = [&](bool act, int start, int& ex, int& cnt, uint8_t* wdst) {
-        int P = start, c = 0;
-        for (int it = 0; it < guard; it++) {
-            const bool go = act && P > bot;
-            if (!ballot(go)) break;
-            if (go) {
-                const uint32_t e = ((const volatile LDSA uint16_t*)tab)[bits(P - tl)];
-                if (wdst) wdst[c] = (uint8_t)e;
-                P -= (int)(e >> 8);
-                c++;
-            }
-        }
-        if (act) { ex = P; cnt = c; }
-    };
-    int start = lane == 0 ? P0 : top, ex = 0, cnt = 0;
-    pass(true, start, ex, cnt, nullptr);
-    for (int round = 0; round < LZH_WAVE; round++) {   // until every share starts where the previous one ends
-        const int prev = (int)lane_gather((uint32_t)ex, lane > 0 ? lane - 1 : 0);
-        const int want = lane == 0 ? P0 : prev;
-        const bool ch = want != start;
-        if (!ballot(ch)) break;
-        // decode from the new start (A) alongside the chain already counted from the old one (B), always the
-        // higher of the two, until they meet -- the rest is the counted chain -- or A leaves the share
-        int PA = want, cA = 0, PB = start, cB = 0;
-        bool met = false;
-        for (int it = 0; it < 2 * guard; it++) {
-            met = met || (ch && PA == PB);
-            const bool go = ch && !met && PA > bot;
-            if (!ballot(go)) break;
-            if (go) {
-                const bool a = PA > PB;
-                const uint32_t e = ((const volatile LDSA uint16_t*)tab)[bits((a ? PA : PB) - tl)];
-                const int nb = (int)(e >> 8);
-                PA -= a ? nb : 0;
-                cA += a ? 1 : 0;
-                PB -= a ? 0 : nb;
-                cB += a ? 0 : 1;
-            }
-        }
-        if (ch) {
-            if (met) {
-                cnt = cA + (cnt - cB);   // (ex: the counted chain's exit)
-            } else {
-                ex = PA;
-                cnt = cA;
-            }
-            start = want;
-        }
-    }
-    const int incl = groups::wave_incl_scan(cnt);
-    const int total = rdlanei(incl, LZH_WAVE - 1);
-    const bool exact = total == nsym && rdlanei(ex, LZH_WAVE - 1) == lo;
-    if (exact) {
-        uint8_t* dst = out + (uint64_t)jf * chunk_size + uni(J->dst) + (uint64_t)j * jseg + (incl - cnt);
-        int ex2 = 0, cnt2 = 0;
-        pass(true, start, ex2, cnt2, dst);
-    } else if (lane == 0) {   // not consumed exactly: X2's verdict (the one-wave decoder) or corrupt
-        if (uni(J->x2)) {
-            atomicMax(&zst[jf], kLegacy);
-        } else if (atomicMax(&zst[jf], kDone) != kDone) {
-            status[jf] = ZC;
-        }
-    }
+#include "zstdd_hufpar_body.inc"
 }
 
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_huf_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets, uint64_t n_total,
                     uint64_t chunk_size, uint8_t* out, int32_t* status, uint8_t* zt, int32_t* zst,
                     const zsplit::ZHuf* jobs, const uint32_t* njobs, unsigned long long* stats, int par) {
-    zstd_huf<4>(packed, packed_readable, offsets, n_total, chunk_size, out, status, zt, zst, jobs, njobs, stats, par);
+    zstd_huf<4>(packed, packed_readable, offsets, zsplit::UniformOut{n_total, chunk_size, out}, status, zt, zst, jobs,
+                njobs, stats, par);
 }
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_huf8_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets, uint64_t n_total,
                      uint64_t chunk_size, uint8_t* out, int32_t* status, uint8_t* zt, int32_t* zst,
                      const zsplit::ZHuf* jobs, const uint32_t* njobs, unsigned long long* stats, int par) {
-    zstd_huf<8>(packed, packed_readable, offsets, n_total, chunk_size, out, status, zt, zst, jobs, njobs, stats, par);
+    zstd_huf<8>(packed, packed_readable, offsets, zsplit::UniformOut{n_total, chunk_size, out}, status, zt, zst, jobs,
+                njobs, stats, par);
 }
 
 // The sequence / execution plan: frames the header and literal kernels left at kGo, split by their sequence
@@ -3286,31 +3172,7 @@ lzh_zstd_exec_kernel(const uint8_t* packed, uint64_t packed_readable, const uint
     const uint64_t chunk = which < 0 ? blockIdx.x : (which == 0 ? flist[blockIdx.x] : flist[nchunks - 1 - blockIdx.x]);
     const uint64_t ooff = chunk * chunk_size;
     if (ooff >= n_total || zst[chunk] != zsplit::kGo) return;   // (the header / literal kernels' verdict first)
-    const int sv = zfr[chunk].sv;                                // then the sequence kernel's
-    if (sv != zsplit::kGo) {
-        if (lane == 0) {
-            if (sv == zsplit::kLegacy) {
-                zst[chunk] = zsplit::kLegacy;
-            } else {
-                status[chunk] = sv;
-                zst[chunk] = zsplit::kDone;
-            }
-        }
-        return;
-    }
-    const int part = (int)min(chunk_size, n_total - ooff);
-    const uint64_t ioff = offsets[chunk];
-    const int cs = (int)csizes[chunk];
-    const uint64_t readable = ioff < packed_readable ? min<uint64_t>(packed_readable - ioff, (uint64_t)cs + 16) : 0;
-    Bytes rin, rout, lout;
-    rin.init(packed + ioff, readable);
-    rout.init(out + ooff, (uint64_t)part);
-    lout.init(out + ooff, (uint64_t)part + 3);
-    const zsplit::ZLayout Z = zsplit::zlayout(chunk_size);
-    zstdd::ZSink O{(LDSA uint8_t*)win, rout, 0, 0};
-    const int r = zsplit::exec_frame(rin, rout, lout, O, (LDSA uint8_t*)win + zstdd::kZW, zt + chunk * Z.stride, Z,
-                                     zfr[chunk], lane);
-    if (lane == 0) status[chunk] = r;
+#include "zstdd_exec_body.inc"
 }
 
 #ifndef LZH_ZSTD_MINW
@@ -3328,27 +3190,7 @@ lzh_zstd_decompress_kernel(const uint8_t* packed, uint64_t packed_readable, cons
     if (ooff >= n_total) return;
     if (zsel && zsel[chunk] != zsplit::kLegacy) return;   // (decoded by the split kernels)
     const int part = (int)min(chunk_size, n_total - ooff);
-    const uint64_t ioff = offsets[chunk];
-    const int cs = (int)csizes[chunk];
-    // (+16: whole-dword reads of the frame's last bytes; bytes past the frame are never used)
-    const uint64_t readable = ioff < packed_readable ? min<uint64_t>(packed_readable - ioff, (uint64_t)cs + 16) : 0;
-    Bytes rin, rout;
-    rin.init(packed + ioff, readable);
-    rout.init(out + ooff, (uint64_t)part);
-    int r;
-    if (cs == part) {                                  // stored raw by the chunk loop (lzbench.cpp:284-288)
-        copy_raw(rin, rout, part, lane);
-        r = part;
-    } else {
-        zstdd::ZSink O{(LDSA uint8_t*)L.win, rout, 0, 0};
-        for (int i = lane; i < 36 + 53; i += LZH_WAVE) L.base[i] = i < 36 ? zstdd::kLLBase[i] : zstdd::kMLBase[i - 36];
-        wave_lds_fence();
-        Bytes lout;
-        lout.init(out + ooff, (uint64_t)part + 3);
-        r = zstdd::decode_frame(rin, lout, cs, O, L, part, lane, stats);
-        if (r > 0) O.flush(r, lane);
-    }
-    if (lane == 0) status[chunk] = r;
+#include "zstdd_frame_body.inc"
 }
 
 #include "launch.h"
@@ -3442,6 +3284,24 @@ extern "C" int lzh_debug_zstd_huf_sections(int hj) {
     g_zstd_huf_sections = hj;
     return 0;
 }
+// the current device's CUs (0: unknown)
+static int zstd_cus() {
+    static int hcus[64];
+    int hdev = 0;
+    (void)hipGetDevice(&hdev);
+    if (hdev < 0 || hdev >= 64) hdev = 0;
+    if (!hcus[hdev] && hipDeviceGetAttribute(&hcus[hdev], hipDeviceAttributeMultiprocessorCount, hdev) != hipSuccess)
+        hcus[hdev] = 0;
+    return hcus[hdev];
+}
+// Huffman sections a wave for a launch of nchunks frames
+// (8 sections a wave once the frames -- about one Huffman job each -- fill 8 x 4 waves per CU)
+static int zstd_huf_sections(uint32_t nchunks) {
+    const int cus = zstd_cus();
+    return (g_zstd_huf_sections ? g_zstd_huf_sections == 8 : cus > 0 && (uint64_t)nchunks >= 32ull * (uint64_t)cus) ? 8 : 4;
+}
+// (the ragged launcher of zstd_ragged_decode_hip.hip: the same hooks, the same rule)
+LzhZstdHooks lzh_zstd_hooks(uint32_t nchunks) { return {g_zstd_legacy, g_zstd_hufpar, zstd_huf_sections(nchunks)}; }
 extern "C" int lzh_debug_force_decode_window(int kw) {
     if (kw != 0 && kw != 4096 && kw != 8192 && kw != 16384) return -1;
     g_force_window = kw;
@@ -3558,10 +3418,6 @@ hipError_t lzh_launch_zstd_decompress(const uint8_t* packed, uint64_t packed_rea
         (void)hipMemsetAsync(njobs, 0, 4, s);
         hipLaunchKernelGGL(lzh_zstd_hdr_kernel, dim3(nchunks), dim3(64), 0, s, packed, packed_readable, offsets, csizes,
                            n_total, chunk_size, out, status, zt, zst, zfr, stats, jobs, njobs);
-        static int hcus[64];
-        int hdev = 0;
-        (void)hipGetDevice(&hdev);
-        if (hdev < 0 || hdev >= 64) hdev = 0;
         // the sequence kernel needs the header kernel's output only (its verdict goes to zfr[].sv): it runs
         // on a side stream beside the literal kernels, launched first -- its waves, one per SIMD at config 5's
         // share, take their SIMDs and the literal waves fill the rest -- and the execution kernel joins both
@@ -3575,11 +3431,10 @@ hipError_t lzh_launch_zstd_decompress(const uint8_t* packed, uint64_t packed_rea
         const bool side = !LZH_ZSTD_STATS && g_zstd_side && lzh_side_stream(s, sq[0], fork[0], join[0], 0) &&
                           lzh_side_stream(s, sq[1], fork[1], join[1], 1);
         const unsigned sgrid = (nchunks + zsplit::kFPW - 1) / zsplit::kFPW;
-        if (!hcus[hdev] && hipDeviceGetAttribute(&hcus[hdev], hipDeviceAttributeMultiprocessorCount, hdev) != hipSuccess)
-            hcus[hdev] = 0;
+        const int cus = zstd_cus();
         // (the plan only while the sequence waves leave LDS room beside them -- at most 2 of a CU's 4 -- for the
         // literal kernels, whose end the execution of the short frames waits for; else one sequence launch)
-        const bool plan = side && g_zstd_plan && hcus[hdev] > 0 && sgrid <= 2u * (unsigned)hcus[hdev];
+        const bool plan = side && g_zstd_plan && cus > 0 && sgrid <= 2u * (unsigned)cus;
         if (plan) {
             hipLaunchKernelGGL(lzh_zstd_plan_kernel, dim3(1), dim3(1024), 0, s, (const int32_t*)zst,
                                (const zsplit::ZFrame*)zfr, nchunks, flist, fcnt);
@@ -3607,9 +3462,7 @@ hipError_t lzh_launch_zstd_decompress(const uint8_t* packed, uint64_t packed_rea
         (void)hipMemsetAsync(d_hst, 0, 8 * sizeof(unsigned long long), s);
         hstats = d_hst;
 #endif
-        // (8 sections a wave once the frames -- about one Huffman job each -- fill 8 x 4 waves per CU)
-        const int hj = (g_zstd_huf_sections ? g_zstd_huf_sections == 8
-                                            : hcus[hdev] > 0 && (uint64_t)nchunks >= 32ull * (uint64_t)hcus[hdev]) ? 8 : 4;
+        const int hj = zstd_huf_sections(nchunks);
         hipLaunchKernelGGL(hj == 8 ? lzh_zstd_huf8_kernel : lzh_zstd_huf_kernel, dim3((unsigned)((maxjobs + hj - 1) / hj)),
                            dim3(64), 0, s, packed, packed_readable, offsets, n_total, chunk_size, out, status, zt, zst,
                            (const zsplit::ZHuf*)jobs, (const uint32_t*)njobs, hstats, g_zstd_hufpar);
@@ -3687,6 +3540,23 @@ hipError_t lzh_launch_zstd_decompress(const uint8_t* packed, uint64_t packed_rea
     return hipGetLastError();
 }
 
+// the sequence kernel alone, every frame in one launch on s (ragged batches: frames of up to slot_bytes)
+hipError_t lzh_launch_zstd_seq(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                               uint64_t slot_bytes, uint32_t nchunks, int32_t* status, uint8_t* zt, const int32_t* zst,
+                               void* zfr, hipStream_t s) {
+    hipLaunchKernelGGL(lzh_zstd_seq_kernel, dim3((nchunks + zsplit::kFPW - 1) / zsplit::kFPW), dim3(64), 0, s, packed,
+                       packed_readable, offsets, slot_bytes, nchunks, status, zt, zst, (zsplit::ZFrame*)zfr,
+                       (unsigned long long*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, -1);
+    return hipGetLastError();
+}
+
+// the sizes temp_layout.h lays a ragged batch's split-decoder temp out with (frames of up to chunk bytes)
+LzhZstdSplitSizes lzh_zstd_split_sizes(uint64_t chunk, uint64_t nchunks) {
+    const zsplit::ZLayout Z = zsplit::zlayout(chunk);
+    return {(size_t)Z.stride, (size_t)zsplit::zdummy_bytes(nchunks), sizeof(zsplit::ZFrame),
+            (size_t)(Z.bmax * sizeof(zsplit::ZHuf))};
+}
+
 // bytes of the split decoder's temp for n bytes in chunks of chunk_size (per frame: blocks, block
 // positions, sequence tables, sequences; then the frame states and frame fields)
 // (0 below lzh_zstd_split_min: the layout reserves two block slots (~17 KiB) and 2 x chunk of sequence
@@ -3699,3 +3569,4 @@ size_t lzh_zstd_decode_temp(uint64_t n, uint64_t chunk_size) {
            k * Z.bmax * sizeof(zsplit::ZHuf) + 256 + ((k * 4 + 8 + 255) & ~255ull);   // (+ the plan's frame list, counts)
 }
 #endif   // LZH_DEVICE_FUNCTIONS_ONLY
+#endif   // (the split decoder)

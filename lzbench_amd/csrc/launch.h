@@ -42,8 +42,8 @@ size_t lzh_zstd_scratch_stride(size_t chunk_size, int level);
 int lzh_zstd_level_ok(int level, size_t chunk_size);
 // dynamic LDS of the zstd match kernels for frames of up to chunk_size bytes (0: the hash table lives in scratch)
 uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size);
-// ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip; include/lzbench_hip.h 3c): chunk i =
-// in_bytes[i] bytes at in_ptrs[i]; staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes)
+// ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip, zstd_ragged_split_hip.hip;
+// include/lzbench_hip.h 3c): chunk i = in_bytes[i] bytes at in_ptrs[i]; staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes)
 // lays them out (fstride: its rec_stride, the scratch areas' distance, at least lzh_zstd_scratch_stride(max_bytes,
 // level)).  Every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 / status[i] = -1 and none of its
 // slots is touched.
@@ -53,6 +53,32 @@ hipError_t lzh_launch_zstd_ragged(const void* const* in_ptrs, const uint64_t* in
 hipError_t lzh_launch_zstd_decompress_ragged(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                              const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
                                              uint64_t max_bytes, int32_t* status, uint32_t nchunks, hipStream_t s);
+// the same through the four-kernel split decoder (zstd_ragged_split_hip.hip); split: its temp regions
+// (ZstdRaggedSplitTemp, temp_layout.h), laid out for nchunks frames of up to max_bytes.  Frames it leaves decode in
+// the one-wave kernel; with lzh_debug_zstd_legacy(1) the call is the one above.
+struct LzhZstdSplitTemp {
+    uint8_t* frames;     // nchunks per-frame areas, the sequence waves' dummy words right after them
+    int32_t* state;      // nchunks frame states (kGo 0, kLegacy 1, kDone 2)
+    void* zfr;           // nchunks frame fields
+    uint32_t* njobs;     // the Huffman jobs' counter
+    void* jobs;          // nchunks x (blocks per frame) Huffman jobs
+};
+hipError_t lzh_launch_zstd_decompress_ragged_split(const uint8_t* packed, uint64_t packed_readable,
+                                                   const uint64_t* offsets, const uint32_t* csizes,
+                                                   void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
+                                                   int32_t* status, uint32_t nchunks, const LzhZstdSplitTemp& split,
+                                                   hipStream_t s);
+// decode_hip.hip, for the ragged launcher and its layout: the sizes of the split decoder's temp for nchunks frames of
+// up to `chunk` bytes (a frame's area, the dummy words, a frame's fields, a frame's Huffman jobs); the test hooks
+// lzh_debug_zstd_legacy / _hufpar and the Huffman sections a wave (4 or 8: the hook, else by nchunks and the device's
+// CUs); the sequence kernel, which knows no output geometry, over every frame on s
+struct LzhZstdSplitSizes { size_t stride, dummy, frame_fields, frame_jobs; };
+LzhZstdSplitSizes lzh_zstd_split_sizes(uint64_t chunk, uint64_t nchunks);
+struct LzhZstdHooks { int legacy, hufpar, huf_sections; };
+LzhZstdHooks lzh_zstd_hooks(uint32_t nchunks);
+hipError_t lzh_launch_zstd_seq(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                               uint64_t slot_bytes, uint32_t nchunks, int32_t* status, uint8_t* zt, const int32_t* zst,
+                               void* zfr, hipStream_t s);
 // frame_size / bpf: framed layouts (LZ4 frame, nvcomp container) -- block i is block i mod bpf of
 // frame i / bpf (frames of frame_size bytes cut into blocks of chunk_size); bpf <= 1: plain chunks
 hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,

@@ -162,3 +162,33 @@ static inline DecodeTemp ragged_decode_temp(size_t nchunks) {
     t.total = c.at;
     return t;
 }
+
+// ---- ragged zstd decompression with the four-kernel split decoder: the scanned offsets where ragged_decode_temp
+// puts them, then the uniform decoder's per-frame layout for nchunks frames of max_bytes (decode_hip.hip zsplit):
+//   nchunks frame areas of `stride` (blocks, tables, sequence records) | the sequence waves' dummy words, right
+//   after them: the kernels address both from `frames` | frame states (i32) | frame fields | the Huffman jobs'
+//   counter | the Huffman jobs
+// No plan list: every launch is on the caller's stream.  ok = false (total 0): max_bytes below lzh_zstd_split_min
+// or above 16 MiB, no split decoder.
+struct ZstdRaggedSplitTemp {
+    bool ok;
+    size_t stride, scan, frames, dummy, state, fields, njobs, jobs, total;
+    size_t frames_bytes, dummy_bytes, state_bytes, fields_bytes, jobs_bytes;
+};
+static inline ZstdRaggedSplitTemp zstd_ragged_split_temp(size_t nchunks, size_t max_bytes) {
+    ZstdRaggedSplitTemp t = {};
+    t.ok = max_bytes >= lzh_zstd_split_min && max_bytes <= kLz4SplitMax;
+    if (!t.ok) return t;
+    const LzhZstdSplitSizes z = lzh_zstd_split_sizes(max_bytes, nchunks);
+    TempCursor c;
+    t.stride = z.stride;
+    t.scan = c.take((nchunks + 1) * sizeof(uint64_t), kGap);
+    t.frames = c.take(t.frames_bytes = nchunks * z.stride);   // (a multiple of 256: the dummy words follow at once)
+    t.dummy = c.take(t.dummy_bytes = z.dummy);
+    t.state = c.take(t.state_bytes = nchunks * 4);
+    t.fields = c.take(t.fields_bytes = nchunks * z.frame_fields);
+    t.njobs = c.take(4);
+    t.jobs = c.take(t.jobs_bytes = nchunks * z.frame_jobs, kGap);
+    t.total = c.at;   // (above ragged_decode_temp's: a frame area alone is over 17 KiB)
+    return t;
+}

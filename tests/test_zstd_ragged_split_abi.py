@@ -1,0 +1,129 @@
+"""CPU: the split-decoder side of the ragged zstd calls (include/lzbench_hip.h 3c) without a device -- the new
+sizing function, the debug layout it shares with the launcher, and the async call's argument checks (all made
+before any HIP call)."""
+import numpy as np
+import pytest
+
+import lzbench_amd as L
+
+ZSTD = L.LZH_CODEC_ZSTD
+OK, EARG, ESPACE = 0, -1, -3
+FAKE = 0x1000   # a non-null "device pointer": the checks under test return before anything reads it
+MAX = 16 << 20
+SPLIT_MIN = 16384
+SIZES = [SPLIT_MIN, 16385, 65536, 70000, 131072, 131073, 200000, 262144, 262145, 300000, 1 << 20, (1 << 20) + 1, MAX]
+COUNTS = [0, 1, 2, 7, 8, 9, 255, 256, 257, 1000, 8192, 16384]
+REGIONS = ["offsets", "frames", "dummy", "states", "fields", "njobs", "jobs"]
+
+
+def split_bytes(maxb, k):
+    return L.lib().lzh_zstd_ragged_decompress_split_temp_bytes(maxb, k)
+
+
+def small_bytes(maxb, k):
+    return L.lib().lzh_zstd_ragged_decompress_temp_bytes(maxb, k)
+
+
+def layout(maxb, k):
+    out = np.zeros(16, np.uint64)
+    rc = L.lib().lzh_debug_zstd_ragged_split_layout(maxb, k, out.ctypes.data)
+    return rc, [int(v) for v in out]
+
+
+def _decompress(lib, nchunks, maxb, temp, packed=FAKE, cs=FAKE, ptrs=FAKE, sizes=FAKE, st=FAKE, tp=FAKE):
+    return lib.lzh_zstd_decompress_ragged_async(packed, 1 << 20, cs, None, ptrs, sizes, nchunks, maxb, st, tp, temp, None)
+
+
+def test_the_symbols_exist():
+    lib = L.lib()
+    assert lib.lzh_zstd_ragged_decompress_split_temp_bytes is not None
+    assert lib.lzh_debug_zstd_ragged_split_layout is not None
+
+
+def test_where_there_is_a_split_decoder():
+    for k in (0, 1, 4, 1000):
+        assert split_bytes(SPLIT_MIN - 1, k) == 0
+        assert split_bytes(MAX + 1, k) == 0
+        assert split_bytes(0, k) == 0
+        assert split_bytes(SPLIT_MIN, k) > 0
+        assert split_bytes(MAX, k) > 0
+
+
+def test_sizing_is_monotone_and_never_below_the_one_wave_answer():
+    for maxb in SIZES:
+        prev = 0
+        for k in COUNTS:
+            v = split_bytes(maxb, k)
+            assert v >= prev and v > 0, (maxb, k)
+            assert v >= small_bytes(maxb, k) > 0, (maxb, k)
+            prev = v
+    for k in COUNTS:
+        prev = 0
+        for maxb in SIZES:
+            v = split_bytes(maxb, k)
+            assert v >= prev, (maxb, k)
+            prev = v
+
+
+def test_sizing_follows_the_uniform_decoders_layout():
+    """Both answers come from the same per-frame layout (the uniform one also holds the plan's frame list)."""
+    lib = L.lib()
+    for maxb in [s for s in SIZES if s <= (1 << 20) + 1]:
+        for k in [c for c in COUNTS if c > 0]:
+            uni = lib.lzh_decompress_temp_bytes(ZSTD, k * maxb, maxb)
+            assert abs(split_bytes(maxb, k) - uni) <= 64 * k + 4096, (maxb, k, split_bytes(maxb, k), uni)
+    assert abs(split_bytes(MAX, 3) - lib.lzh_decompress_temp_bytes(ZSTD, 3 * MAX, MAX)) <= 64 * 3 + 4096
+
+
+def test_debug_layout_regions_are_disjoint_and_inside_the_sizing_answer():
+    for maxb in (SPLIT_MIN, 70000, 131072, 300000, MAX):
+        for k in (0, 1, 9, 1000):
+            rc, v = layout(maxb, k)
+            assert rc == OK
+            total = v[15]
+            assert total == split_bytes(maxb, k)
+            regs = sorted((v[2 * i], v[2 * i + 1], REGIONS[i]) for i in range(7))
+            end = 0
+            for off, size, name in regs:
+                assert off >= end, (maxb, k, name)             # (in order, no overlap)
+                assert off % 256 == 0, (maxb, k, name)
+                end = off + size
+            assert end <= total
+            by = {REGIONS[i]: (v[2 * i], v[2 * i + 1]) for i in range(7)}
+            assert by["offsets"] == (0, 8 * (k + 1))            # where the one-wave call scans them to
+            assert by["frames"][1] == k * v[14] and v[14] % 256 == 0
+            assert by["dummy"][0] == by["frames"][0] + by["frames"][1]   # the kernels address both from `frames`
+            assert by["states"][1] == 4 * k and by["njobs"][1] == 4
+            assert by["jobs"][1] >= 64 * k * ((maxb + 131071) // 131072)  # a Huffman job per block
+    # a frame's area holds its sequence records, 8 bytes for every 4 bytes of output
+    assert layout(131072, 1)[1][14] >= 2 * 131072
+
+
+def test_debug_layout_refuses_what_the_sizing_refuses():
+    out = np.zeros(16, np.uint64)
+    lib = L.lib()
+    assert lib.lzh_debug_zstd_ragged_split_layout(SPLIT_MIN - 1, 4, out.ctypes.data) == EARG
+    assert lib.lzh_debug_zstd_ragged_split_layout(MAX + 1, 4, out.ctypes.data) == EARG
+    assert lib.lzh_debug_zstd_ragged_split_layout(65536, 4, None) == EARG
+
+
+@pytest.mark.parametrize("maxb", [65536, 300000, SPLIT_MIN, SPLIT_MIN - 1])
+def test_argument_checks_without_a_device(maxb):
+    """The order of the checks and the LZH_ESPACE threshold are those of the one-wave call, whatever temp_bytes is."""
+    lib = L.lib()
+    dt, zt = small_bytes(maxb, 4), split_bytes(maxb, 4)
+    assert dt > 0 and (zt >= dt or zt == 0)
+    for temp in (0, dt, zt, 1 << 40):
+        for null in ("packed", "cs", "ptrs", "sizes", "st", "tp"):
+            assert _decompress(lib, 4, maxb, temp, **{null: None}) == EARG, (null, temp)
+        assert _decompress(lib, 0, maxb, temp, None, None, None, None, None, None) == OK
+        assert _decompress(lib, 4, MAX + 1, temp) == EARG
+        assert _decompress(lib, 0x80000000, maxb, temp) == EARG
+    assert _decompress(lib, 4, maxb, dt - 1) == ESPACE
+
+
+def test_python_mirror():
+    """RaggedCodec's checks come before any torch call: no device needed."""
+    for codec in ("lz4", "snappy"):
+        with pytest.raises(ValueError):
+            L.RaggedCodec(codec, 65536, 4, split_decode=True)

@@ -1,7 +1,9 @@
 """tools/zstd_ragged_perf.py [OUTDIR] -- the measurement of profiles/ragged/README.md, last section: 1 GiB mixed
 as 8,192 entries of 128 KiB, zstd level 1, through the ragged zstd calls and the uniform ones (HIP events, 2 warm-up
 and 12 timed calls each; the uniform call before and after the ragged one, like for like -- one stream, one-wave
-decoder -- then with its defaults).  Writes OUTDIR/zstd_ragged_perf.json (default: bench_out/ in the repository root)."""
+decoder -- then with its defaults; then the split-decode series: the ragged call with the split temp between two
+series of the uniform split decoder on one stream (lzh_debug_zstd_side(0): the kernels the ragged call shares), the
+ragged one-wave call in the same run, and the uniform default).  Writes OUTDIR/zstd_ragged_perf.json (default: bench_out/ in the repository root)."""
 import json
 import os
 import sys
@@ -77,6 +79,30 @@ def main():
     ok = (bool((rc.status[:k] == CHUNK).all()) and bool((dc.status == CHUNK).all())
           and torch.equal(out[:N], d_in[:N]) and torch.equal(dc.out[:N], d_in[:N]))
     res["decompress_same_bytes"] = bool(ok)
+
+    # split decode: like for like = the uniform call's four-kernel decoder with every kernel on the caller's stream
+    rs = L.RaggedCodec("zstd", CHUNK, k, LEVEL, max_total_bytes=N, split_decode=True)
+    res["ragged_split_decompress_temp"] = int(rs.dtemp.numel())
+    assert rs.dtemp.numel() == lib.lzh_zstd_ragged_decompress_split_temp_bytes(CHUNK, k) > rc.dtemp.numel()
+    out.zero_()
+    split = lambda: rs.decompress_arrays(d_dst, k, packed=rc.packed, csizes=rc.csizes, offsets=rc.offsets)  # noqa: E731
+    lib.lzh_debug_zstd_side(0)
+    res["split_uniform_one_stream_a"] = timed(lambda: dc.decompress())
+    res["split_ragged"] = timed(split)
+    res["split_uniform_one_stream_b"] = timed(lambda: dc.decompress())
+    lib.lzh_debug_zstd_side(1)
+    torch.cuda.synchronize()
+    ok2 = bool((rs.status[:k] == CHUNK).all()) and torch.equal(out[:N], d_in[:N])
+    res["split_ragged_onewave"] = timed(lambda: rc.decompress_arrays(d_dst, k))
+    res["split_uniform_default"] = timed(lambda: dc.decompress())
+    v = np.zeros(16, np.uint64)
+    assert lib.lzh_debug_zstd_ragged_split_layout(CHUNK, k, v.ctypes.data) == 0
+    split()
+    torch.cuda.synchronize()
+    st = rs.dtemp[int(v[6]): int(v[6]) + 4 * k].cpu().numpy().view(np.int32)
+    res["split_frames_by_state"] = {str(int(a)): int(b) for a, b in zip(*np.unique(st, return_counts=True))}
+    res["split_same_bytes"] = ok2
+    ok = ok and ok2
     with open(os.path.join(OUT, "zstd_ragged_perf.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res, indent=1))
