@@ -211,6 +211,7 @@ struct SinkT {
             const int t = base + lane;
             const int s = off >= LZH_WAVE ? src0 + t : src0 + (int)((uint32_t)t % (uint32_t)off);
             if (off < len && base > 0) flush(op + base, lane);   // sources in this match's output
+            else maybe_flush(op + base, lane);   // (a match longer than the window must not wrap it while pending)
             wait_vm();
             const uint32_t v = t < len ? out.b_sc1(s) : 0u;
             if (t < len) put(op + t, v);

@@ -7,8 +7,9 @@ packing) on the repo's deterministic corpora.  Stored: sha256 of the packed stre
 compr_sizes (little-endian u64), plus the packed byte count; inputs regenerate from the seeds.
 
 Covers the fast-strategy levels (zstd 1 and 2 where fast, zstd_fast -1..-5), single-block frames
-(-b64, -b128), multi-block frames with Huffman-table repeats and RLE blocks (-b256 .. -b1024,
-the latter beyond the 512 KiB window), raw chunks, tiny and ragged tails.
+(-b64, -b128), multi-block frames with Huffman-table repeats (-b256 .. -b1024, the latter beyond the
+512 KiB window), raw chunks, tiny and ragged tails, and one RLE block (300000 zero bytes at -b256: the
+only one; which format branches the whole set reaches is asserted by tests/test_zstd_census.py).
 Run from the repo root:  python tests/golden/make_zstd_cgolden.py"""
 import hashlib
 import json
@@ -25,11 +26,14 @@ import oracle_lib as O  # noqa: E402
 
 
 def corpus(kind, n, seed):
-    """Synthetic inputs: lzh_datagen corpora, plus zero runs with sparse literals and short runs."""
+    """Synthetic inputs: lzh_datagen corpora, plus zero runs with sparse literals ("zeros": a 7 every 4099 bytes, so
+    no block is one repeated byte), nothing but zeros ("zero") and short runs."""
     if kind == "zeros":
         d = np.zeros(n, np.uint8)
         d[::4099] = 7
         return d
+    if kind == "zero":
+        return np.zeros(n, np.uint8)
     if kind == "runs":
         rng = np.random.default_rng(seed)
         return np.repeat(rng.integers(0, 4, n // 8 + 16, dtype=np.uint8),
@@ -47,6 +51,7 @@ for kind in ("text", "mixed", "runs"):
         CASES.append((kind, 600_000, 131072, level))
 for n in (1, 7, 8, 37, 63, 64, 255, 256, 1023, 1024, 16384, 16385, 65792, 65793):
     CASES.append(("text", n, 131072, 1))
+CASES.append(("zero", 300_000, 262144, 1))              # an RLE block (the second block of the first frame)
 
 
 def main():

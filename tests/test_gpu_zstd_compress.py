@@ -36,6 +36,8 @@ def corpus(kind, n, seed):
         d = np.zeros(n, np.uint8)
         d[::4099] = 7
         return d
+    if kind == "zero":
+        return np.zeros(n, np.uint8)
     if kind == "runs":
         rng = np.random.default_rng(seed)
         return np.repeat(rng.integers(0, 4, n // 8 + 16, dtype=np.uint8),
