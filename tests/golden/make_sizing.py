@@ -6,10 +6,12 @@ sizing.json pins what the sizing calls returned before that was so, for tests/te
 arithmetic: needs the built liblzbench_hip.so, no GPU and no reference build.  Run on the commit whose answers are
 to be pinned (python tests/golden/make_sizing.py); LZH_LIB names another build of the library.
 
-Writes sizing.json: {"grid": {...}, "tables": {function: {codec number: [values in the grid's loop order]}},
-"sha256": digest of the tables}.  Loop order: the arguments in the order of the C declaration, the first one
+Writes sizing.json and, for the ragged zstd calls, sizing_zstd_ragged.json, each {"grid": {...}, "tables":
+{function: {codec number: [values in the grid's loop order]}}, "sha256": digest of the tables}.  Loop order: the arguments in the order of the C declaration, the first one
 outermost.  lzh_debug_ragged_compact_regions gives four values per point; lzh_debug_plan gives, per point, its
-return value and then that many values.
+return value and then that many values.  The ragged zstd calls (levels 1 and -1 where they take one, over
+chunk x nchunks) have one list each, under codec "3"; lzh_debug_zstd_ragged_split_layout gives its 16 values per
+point, or its error code 16 times.
 """
 from __future__ import annotations
 
@@ -68,6 +70,24 @@ def tables(lib) -> dict:
           lambda c: (lib.lzh_ragged_compact_compress_temp_bytes(c, t, m, k) for t in N for m in CH for k in K))
     table("lzh_debug_ragged_compact_regions", regions)
     table("lzh_debug_plan", plan)
+
+    # the ragged zstd calls take no codec: their tables are keyed under zstd's number alone
+    def zstd_table(name, values):
+        out[name] = {"3": [int(v) for v in values]}
+
+    def split_layout():
+        r = (C.c_uint64 * 16)()
+        for m in CH:
+            for k in K:
+                rc = lib.lzh_debug_zstd_ragged_split_layout(m, k, r)
+                yield from (list(r) if rc == 0 else [rc] * 16)
+
+    zstd_table("lzh_zstd_ragged_compress_temp_bytes",
+               (lib.lzh_zstd_ragged_compress_temp_bytes(lv, m, k) for lv in (1, -1) for m in CH for k in K))
+    for name in ("lzh_zstd_ragged_decompress_temp_bytes", "lzh_zstd_ragged_decompress_split_temp_bytes",
+                 "lzh_zstd_ragged_max_packed_bytes"):   # (the last one's first argument is the batch's total bytes)
+        zstd_table(name, (getattr(lib, name)(m, k) for m in CH for k in K))
+    zstd_table("lzh_debug_zstd_ragged_split_layout", split_layout())
     return out
 
 
@@ -75,13 +95,20 @@ def digest(tabs: dict) -> str:
     return hashlib.sha256(json.dumps(tabs, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
 
 
+def files(tabs: dict) -> dict:
+    """{file name: its tables}: the ragged zstd tables have a file of their own, so that adding them left
+    sizing.json, a single line of 190 KB, as it was."""
+    own = {name: t for name, t in tabs.items() if "zstd_ragged" in name}
+    return {"sizing.json": {name: t for name, t in tabs.items() if name not in own}, "sizing_zstd_ragged.json": own}
+
+
 def main():
     import lzbench_amd as L
-    tabs = tables(L.lib())
-    with open(os.path.join(HERE, "sizing.json"), "w") as f:
-        json.dump({"grid": GRID, "tables": tabs, "sha256": digest(tabs)}, f, sort_keys=True, separators=(",", ":"))
-        f.write("\n")
-    print(f"sizing.json: {sum(len(v) for t in tabs.values() for v in t.values())} values, sha256 {digest(tabs)}")
+    for fname, tabs in files(tables(L.lib())).items():
+        with open(os.path.join(HERE, fname), "w") as f:
+            json.dump({"grid": GRID, "tables": tabs, "sha256": digest(tabs)}, f, sort_keys=True, separators=(",", ":"))
+            f.write("\n")
+        print(f"{fname}: {sum(len(v) for t in tabs.values() for v in t.values())} values, sha256 {digest(tabs)}")
 
 
 if __name__ == "__main__":

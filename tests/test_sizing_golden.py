@@ -1,4 +1,4 @@
-"""CPU: every sizing entry point of the device API answers what tests/golden/sizing.json recorded (the temp layouts
+"""CPU: every sizing entry point of the device API answers what tests/golden/sizing*.json recorded (the temp layouts
 of lzbench_amd/csrc/temp_layout.h give the sizes the hand-kept sums gave before them), and the ragged uniform-slot
 compress temp is the uniform call's for the same slots."""
 import importlib.util
@@ -19,19 +19,20 @@ def _maker():
 
 def test_sizing_answers_equal_the_recorded_ones():
     M = _maker()
-    with open(os.path.join(GOLDEN, "sizing.json")) as f:
-        want = json.load(f)
-    assert want["grid"] == M.GRID, "sizing.json was made over another grid"
-    assert M.digest(want["tables"]) == want["sha256"], "sizing.json was edited by hand"
-    got = M.tables(L.lib())
-    assert sorted(got) == sorted(want["tables"])
-    for name, per_codec in want["tables"].items():
-        for codec, values in per_codec.items():
-            have = got[name][codec]
-            assert len(have) == len(values), (name, codec)
-            bad = [(i, a, b) for i, (a, b) in enumerate(zip(have, values)) if a != b]
-            assert not bad, f"{name}, codec {codec}: {len(bad)} answers changed, first (index, now, recorded) {bad[0]}"
-    assert M.digest(got) == want["sha256"]
+    for fname, got in M.files(M.tables(L.lib())).items():   # (sizing.json, and the ragged zstd calls' file)
+        with open(os.path.join(GOLDEN, fname)) as f:
+            want = json.load(f)
+        assert want["grid"] == M.GRID, f"{fname} was made over another grid"
+        assert M.digest(want["tables"]) == want["sha256"], f"{fname} was edited by hand"
+        assert got and sorted(got) == sorted(want["tables"])
+        for name, per_codec in want["tables"].items():
+            assert sorted(got[name]) == sorted(per_codec), name
+            for codec, values in per_codec.items():
+                have = got[name][codec]
+                assert len(have) == len(values), (name, codec)
+                bad = [(i, a, b) for i, (a, b) in enumerate(zip(have, values)) if a != b]
+                assert not bad, f"{name}, codec {codec}: {len(bad)} answers changed, first (index, now, recorded) {bad[0]}"
+        assert M.digest(got) == want["sha256"]
 
 
 def test_ragged_uniform_slots_size_as_the_uniform_call():

@@ -75,6 +75,29 @@ def test_sizing_follows_the_uniform_decoders_layout():
     assert abs(split_bytes(MAX, 3) - lib.lzh_decompress_temp_bytes(ZSTD, 3 * MAX, MAX)) <= 64 * 3 + 4096
 
 
+def test_uniform_and_ragged_sizes_differ_by_a_closed_form():
+    """The uniform and the ragged call describe the same per-frame layout: frames, dummy words, states, fields and
+    the job counter are the same bytes in both, so the two published answers differ by exactly the plan list, the
+    rounding of the jobs region and the two scan regions' gaps:
+      uniform = align(8 (k + 1))       + shared + (jobs + 256)        + align(4 k + 8) + 256
+      ragged  = align(8 (k + 1)) + 256 + shared + (align(jobs) + 256)
+    with align to 256 and jobs = k frames x (blocks of 128 KiB in maxb, and one) x 64 bytes a Huffman job."""
+    lib = L.lib()
+
+    def align(v):
+        return (v + 255) // 256 * 256
+
+    for maxb in SIZES:
+        for k in [c for c in COUNTS if c > 0]:
+            jobs = k * ((maxb + 131071) // 131072 + 1) * 64
+            assert layout(maxb, k)[1][13] == jobs, (maxb, k)
+            plan = align(4 * k + 8)             # the uniform call's frame list and two counts
+            rounding = align(jobs) - jobs       # the ragged call rounds its jobs region, the uniform one does not
+            gaps = 256 - 256                    # the uniform total's trailing gap against the ragged scan region's
+            uni = lib.lzh_decompress_temp_bytes(ZSTD, k * maxb, maxb)
+            assert uni - split_bytes(maxb, k) == plan - rounding + gaps, (maxb, k, uni, split_bytes(maxb, k))
+
+
 def test_debug_layout_regions_are_disjoint_and_inside_the_sizing_answer():
     for maxb in (SPLIT_MIN, 70000, 131072, 300000, MAX):
         for k in (0, 1, 9, 1000):
