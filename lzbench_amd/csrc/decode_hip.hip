@@ -196,9 +196,14 @@ struct SinkT {
         const int src0 = op - off;
         // (reach kWin - 128: the group emitter may have written up to 127 bytes past its end)
         if (src0 >= ringlo && off <= KW - 2 * LZH_WAVE) {
+            // (a period shorter than the wave: the first `per` bytes come from the period before op, the rest
+            // from this match's own output `per` bytes back -- a multiple of the period of at least a wave, so
+            // written by an earlier round and still in the window however long the match is)
+            const int per = off >= LZH_WAVE ? off : off * ((LZH_WAVE + off - 1) / off);
             for (int base = 0; base < len; base += LZH_WAVE) {
                 const int t = base + lane;
-                const int s = off >= LZH_WAVE ? src0 + t : src0 + (int)((uint32_t)t % (uint32_t)off);
+                const int s = off >= LZH_WAVE ? src0 + t
+                            : (t < per ? src0 + (int)((uint32_t)t % (uint32_t)off) : op + t - per);
                 const uint32_t v = get(s);
                 if (t < len) put(op + t, v);
                 maybe_flush(op + min(base + LZH_WAVE, len), lane);

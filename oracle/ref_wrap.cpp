@@ -29,6 +29,7 @@
 #include <vector>
 #include "lz4.h"
 #include "lz4frame.h"
+#include "lz4hc.h"
 #include "snappy.h"
 #define ZSTD_STATIC_LINKING_ONLY   /* ZSTD_compress_advanced, as lzbench uses it */
 #include "zstd.h"
@@ -40,6 +41,8 @@ extern "C" {
 int ref_lz4_version(void) { return LZ4_versionNumber(); }
 int ref_lz4_compress_fast(const char* s, char* d, int n, int cap, int acc) { return LZ4_compress_fast(s, d, n, cap, acc); }
 int ref_lz4_compress_default(const char* s, char* d, int n, int cap) { return LZ4_compress_default(s, d, n, cap); }
+/* the HC parser (levels 3..12): valid LZ4 blocks the fast parser never writes -- decoder test fixtures */
+int ref_lz4_compress_hc(const char* s, char* d, int n, int cap, int level) { return LZ4_compress_HC(s, d, n, cap, level); }
 int ref_lz4_decompress_safe(const char* s, char* d, int csize, int cap) { return LZ4_decompress_safe(s, d, csize, cap); }
 int ref_lz4_decompress_fast(const char* s, char* d, int osize) { return LZ4_decompress_fast(s, d, osize); }
 size_t ref_snappy_compress(const char* s, size_t n, char* d) { size_t out = 0; snappy::RawCompress(s, n, d, &out); return out; }

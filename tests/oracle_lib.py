@@ -64,6 +64,11 @@ def have_ref() -> bool:
     return os.path.exists(REF_PATH)
 
 
+def have_ref_hc() -> bool:
+    """the reference build is present and has the LZ4 HC shim (oracle/ref_wrap.cpp ref_lz4_compress_hc)"""
+    return have_ref() and hasattr(ref(), "ref_lz4_compress_hc")
+
+
 def ref():
     global _ref
     if _ref is None:
@@ -71,6 +76,9 @@ def ref():
         L.ref_lz4_version.restype = C.c_int
         L.ref_lz4_compress_fast.restype = C.c_int
         L.ref_lz4_compress_fast.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "ref_lz4_compress_hc"):   # (a libref.so built before the HC shim lacks it: have_ref_hc())
+            L.ref_lz4_compress_hc.restype = C.c_int
+            L.ref_lz4_compress_hc.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int]
         L.ref_lz4_decompress_safe.restype = C.c_int
         L.ref_lz4_decompress_safe.argtypes = [_P, _P, C.c_int, C.c_int]
         L.ref_snappy_compress.restype = _SZ
