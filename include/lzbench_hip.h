@@ -251,8 +251,9 @@ int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t ma
  * Compress temp: nchunks staging slots, then nchunks scratch areas of the two zstd kernels (sequences, literals,
  * a block attempt, a Huffman stream, the hash table), every one sized for max_chunk_bytes: nchunks x (the staging
  * stride + the scratch stride of max_chunk_bytes; 1.26 MiB a chunk at 128 KiB, 278 KiB at 16 KiB), so a skewed
- * batch pays for its largest chunk nchunks times.  There is no compact layout for zstd.  Decompress temp: the
- * scanned offsets (as 3b); the split decoder's temp below is optional.
+ * batch pays for its largest chunk nchunks times; the compact calls at the end of this section size every slot
+ * from its own chunk instead.  Decompress temp: the scanned offsets (as 3b); the split decoder's temp below is
+ * optional.
  * lzh_zstd_ragged_max_packed_bytes: zstd expands small chunks (1..64 bytes become size + 9, which is not stored
  * raw); the bound is the sum of the per-chunk bounds lzh_stage_stride(LZH_CODEC_ZSTD, .) is sized for.
  * Decoding: any frame of lzbench's shape, also with the content checksum; the verdicts of lzh_decompress_async.
@@ -289,6 +290,63 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
  * counter, 6 the Huffman jobs; out[14] = a frame area's size, out[15] = the sizing answer (16 values).  Host
  * arithmetic only; LZH_EARG where the sizing answer is 0 or out is null. */
 int lzh_debug_zstd_ragged_split_layout(size_t max_chunk_bytes, size_t nchunks, uint64_t* out);
+
+/* Compact compress layout: lzh_zstd_compress_ragged_async with every chunk's staging slot and scratch slot sized
+ * from that chunk's own d_in_bytes[i] and the level (256-aligned) and placed by an exclusive scan on the device,
+ * so temp grows with the batch's total bytes plus a constant per chunk, not with nchunks x (the slots of
+ * max_chunk_bytes).  A chunk of n bytes takes a staging slot of lzh_stage_stride(LZH_CODEC_ZSTD, n) and a
+ * scratch slot of what the two zstd kernels address for a frame of that size alone: about 8 x min(n, 128 KiB)
+ * + 6.5 KiB for sequences, literals, the block attempt and a Huffman stream, and the frame's own hash table
+ * (4 << hashLog bytes: up to 16 x n for a small chunk, at most 256 KiB; not monotone in n, since hashLog drops
+ * where n enters the next size class of ZSTD_getParams).  An empty chunk takes the slots of a 1-byte chunk
+ * (6912 bytes of scratch; it touches the first 1024).  The scratch region is sized as the smaller of
+ * nchunks x the largest slot of any size up to max_chunk_bytes at that level and the sum of three bounds: the
+ * areas before the table, min(8 x total_in_bytes, nchunks x 8 x min(max_chunk_bytes, 128 KiB)) -- one large
+ * chunk pays for one block, not for its size -- 6656 bytes a chunk, and the tables, min(16 x total_in_bytes
+ * + 512 x nchunks, nchunks x the largest table up to max_chunk_bytes); the staging region as the smaller of
+ * total + total / 256 + 335 x nchunks and nchunks x the slot of max_chunk_bytes.  The sizing function's own
+ * answers:
+ *   4096 chunks, one of 16 MiB and 4095 of 4 KiB (33,550,336 bytes in all):   867,689,472 bytes (0.81 GiB) at
+ *       level 1 and 465,036,288 (0.43 GiB) at level -1, where lzh_zstd_ragged_compress_temp_bytes answers
+ *       74,381,787,648 (69.27 GiB);
+ *   4096 chunks of 128 KiB:   5,396,071,424 bytes (5.03 GiB) at level 1 against 5,395,972,608 -- a uniform batch
+ *       gains nothing there (the same slots and the four arrays, 98,816 bytes) and only the level's own hash
+ *       table elsewhere (level -1: 4,993,418,240; the uniform-slot layout takes the worst level's).
+ * Levels, the 16 MiB limit, zero-length chunks, the packed output (d_csizes, d_offsets, the packed bytes, the
+ * raw-store rule), packed_cap enforced on the device, the streams (every launch on hip_stream) and the order of
+ * the checks (level / max_chunk_bytes, nchunks == 0: LZH_OK, null pointers, then temp_bytes: LZH_ESPACE) are
+ * those of lzh_zstd_compress_ragged_async; for a batch that keeps the promise below d_csizes, d_offsets and every
+ * packed byte equal that call's.
+ * total_in_bytes: the caller's host-side upper bound of the sum of d_in_bytes[i] over the chunks that are not
+ * larger than max_chunk_bytes -- the sizes live on the device and nothing is read back, the packed_cap rule.
+ * The sizing function's answer covers every batch of at most nchunks chunks, each of at most max_chunk_bytes,
+ * that sums to at most total_in_bytes; it is non-decreasing in each of the three, never above
+ * lzh_zstd_ragged_compress_temp_bytes(level, max_chunk_bytes, nchunks) plus the four per-chunk arrays (two u32,
+ * two u64 of nchunks + 1), and 0 where that function answers 0.  Both functions derive a staging region and a
+ * scratch region from the same four numbers.  On the device a chunk is processed exactly when it is at most
+ * max_chunk_bytes and both of its slots end inside their regions; a chunk that is not (the second case only in a
+ * batch that breaks the promise) gets d_csizes[i] = 0, takes no packed bytes, and no kernel touches a slot for it.
+ * A chunk over max_chunk_bytes takes slots of 0 bytes.  Every slot is addressed through buffer descriptors
+ * bounded by the slot, so nothing is written outside d_temp[0 .. temp_bytes) whatever the sizes on the device say.
+ * Decompression needs no counterpart: lzh_zstd_decompress_ragged_async's small temp is the scanned offsets, and
+ * the split decoder's temp stays sized per largest chunk (not addressed here). */
+size_t lzh_zstd_ragged_compact_compress_temp_bytes(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                   size_t nchunks);
+int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                           size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
+                                           void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
+                                           void* d_temp, size_t temp_bytes, void* hip_stream);
+/* Host mirror of the compact slot placement for host arrays of sizes (host arithmetic only): stage_off[i] and
+ * scratch_off[i] = the offsets of chunk i's slots inside the staging region and the scratch region, processed[i]
+ * = 1 when the device processes chunk i.  Returns LZH_OK, or LZH_EARG where the async call would. */
+int lzh_debug_zstd_ragged_compact_slots(int level, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                        size_t total_in_bytes, uint64_t* stage_off, uint64_t* scratch_off,
+                                        uint8_t* processed);
+/* Debug only, for tests of the placement (it may change with the temp layout): the two regions as byte ranges of
+ * d_temp: out[0], out[1] = offset and size of the staging region, out[2], out[3] = of the scratch region.  Host
+ * arithmetic only; LZH_EARG as above. */
+int lzh_debug_zstd_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                          uint64_t* out);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

@@ -106,6 +106,10 @@ SIGNATURES = {
     "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
     "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_zstd_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
+    "lzh_zstd_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_debug_zstd_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    "lzh_debug_zstd_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
     "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
     "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
@@ -389,7 +393,13 @@ class RaggedCodec:
     leaves a chunk whose slots do not fit uncompressed with csizes[i] = 0).
     zstd / zstd_fast (the fast-strategy levels lzh_level_supported accepts for max_chunk_bytes) go through the
     lzh_zstd_*_ragged calls: one frame per chunk, a staging slot and a scratch area of the zstd kernels per chunk,
-    each sized for max_chunk_bytes; compact=True raises ValueError (there is no compact layout for zstd).
+    each sized for max_chunk_bytes.  compact_scratch=True (zstd only, else ValueError) sizes both from each chunk's
+    own size and the level instead (lzh_zstd_compress_ragged_compact_async): the temp grows with max_total_bytes
+    (at most 25 x: a small chunk's hash table is several times the chunk) plus 7.5 KiB per chunk, a large chunk
+    pays for one 128 KiB block and not for its size, the temp never passes the other layout's by more than four
+    small arrays, the output is the same, and a batch must keep its total within max_total_bytes
+    as with compact=True.  compact=True itself raises ValueError for zstd (the LZ4 / snappy calls refuse the
+    codec): compact_scratch is the zstd option.
     split_decode=True (zstd only, else ValueError) sizes the decompress temp for the four-kernel split decoder
     (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
     batches); where there is none (max_chunk_bytes below 16 KiB) the temp stays the small one and every frame
@@ -398,7 +408,8 @@ class RaggedCodec:
     """
 
     def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
-                 max_total_bytes: Optional[int] = None, compact: bool = False, split_decode: bool = False):
+                 max_total_bytes: Optional[int] = None, compact: bool = False, split_decode: bool = False,
+                 compact_scratch: bool = False):
         import torch
         self.torch = torch
         self.codec = CODECS[codec]
@@ -409,12 +420,18 @@ class RaggedCodec:
         self.compact = compact
         self.zstd = self.codec == LZH_CODEC_ZSTD
         if self.zstd and compact:
-            raise ValueError("ragged batches: zstd has no compact layout")
+            raise ValueError("ragged batches: compact=True is the LZ4 / snappy layout; for zstd pass compact_scratch=True")
+        if compact_scratch and not self.zstd:
+            raise ValueError("ragged batches: compact_scratch is a zstd option (LZ4 / snappy: compact=True)")
+        self.compact_scratch = compact_scratch
         if split_decode and not self.zstd:
             raise ValueError("ragged batches: split_decode is a zstd option")
         self.split_decode = split_decode
         if self.zstd:
-            ct = L.lzh_zstd_ragged_compress_temp_bytes(self.level, max_chunk_bytes, max_chunks)
+            if compact_scratch:
+                ct = L.lzh_zstd_ragged_compact_compress_temp_bytes(self.level, self.max_total, max_chunk_bytes, max_chunks)
+            else:
+                ct = L.lzh_zstd_ragged_compress_temp_bytes(self.level, max_chunk_bytes, max_chunks)
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
             if split_decode:   # (0: no split decoder for chunks of this size)
                 dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
@@ -470,7 +487,10 @@ class RaggedCodec:
         self.k = k
         out = (self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
                self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
-        if self.zstd:
+        if self.zstd and self.compact_scratch:
+            rc = lib().lzh_zstd_compress_ragged_compact_async(self.level, d[0].data_ptr(), d[1].data_ptr(), k,
+                                                              self.max_chunk_bytes, self.max_total, *out)
+        elif self.zstd:
             rc = lib().lzh_zstd_compress_ragged_async(self.level, d[0].data_ptr(), d[1].data_ptr(), k,
                                                       self.max_chunk_bytes, *out)
         elif self.compact:
@@ -480,7 +500,8 @@ class RaggedCodec:
             rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
                                                  self.max_chunk_bytes, *out)
         if rc:
-            name = "lzh_zstd_compress_ragged" if self.zstd else f"lzh_compress_ragged{'_compact' if self.compact else ''}"
+            name = (f"lzh_zstd_compress_ragged{'_compact' if self.compact_scratch else ''}" if self.zstd
+                    else f"lzh_compress_ragged{'_compact' if self.compact else ''}")
             raise RuntimeError(f"{name}_async failed ({rc})")
 
     def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:

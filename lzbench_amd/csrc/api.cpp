@@ -557,6 +557,76 @@ int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d
     return LZH_OK;
 }
 
+// ---- 3c, compact compress layout: every chunk's staging slot and scratch slot sized from its own size and the
+// level (zstd_ragged_slots.h); zstd_compact_temp lays the temp out for the sizing call, the async call and the
+// debug calls ----
+size_t lzh_zstd_ragged_compact_compress_temp_bytes(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                   size_t nchunks) {
+    if (!zstd_ragged_ok(level, max_chunk_bytes)) return 0;
+    return zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks).total;
+}
+
+int lzh_debug_zstd_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                          uint64_t* out) {
+    if (!zstd_ragged_ok(level, max_chunk_bytes) || !out) return LZH_EARG;
+    const ZstdCompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
+    out[0] = t.stage;
+    out[1] = t.reg.stage;
+    out[2] = t.scratch;
+    out[3] = t.reg.scratch;
+    return LZH_OK;
+}
+
+int lzh_debug_zstd_ragged_compact_slots(int level, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                        size_t total_in_bytes, uint64_t* stage_off, uint64_t* scratch_off,
+                                        uint8_t* processed) {
+    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!sizes || !stage_off || !scratch_off || !processed) return LZH_EARG;
+    const LzhZstdCompactRegions reg = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks).reg;
+    uint64_t so = 0, co = 0;
+    for (size_t i = 0; i < nchunks; i++) {   // lzh_zstd_compact_slots_kernel, the two scans, zcompact_span
+        const bool over = sizes[i] > max_chunk_bytes;
+        uint64_t ss = 0, cs = 0;
+        if (!over) lzh_zstd_compact_slot(level, sizes[i], &ss, &cs);
+        stage_off[i] = so;
+        scratch_off[i] = co;
+        processed[i] = !over && so + ss <= reg.stage && co + cs <= reg.scratch;
+        so += ss;
+        co += cs;
+    }
+    return LZH_OK;
+}
+
+int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                           size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
+                                           void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
+                                           void* d_temp, size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
+    if (nchunks > 0x7fffffffu) return LZH_EARG;   // launch grids
+    const ZstdCompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
+    if (temp_bytes < t.total) return LZH_ESPACE;
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    // (the layout's record fields carry the scratch slots: the pack kernel's lookup is the LZ4 / snappy one)
+    const LzhCompactLayout L = {(uint32_t*)(base + t.stage_sz), (uint32_t*)(base + t.scratch_sz),
+                                (uint64_t*)(base + t.stage_off), (uint64_t*)(base + t.scratch_off), t.reg.stage,
+                                t.reg.scratch};
+    {
+        Range range("lzh:compress_kernel");
+        LZH_CHECK(lzh_launch_zstd_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes, k,
+                                          base + t.scratch, L, s));
+    }
+    Range range("lzh:scan_pack");
+    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
+    LZH_CHECK(lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
+                                      (uint8_t*)d_packed, packed_cap, k, L, s));
+    return LZH_OK;
+}
+
 }  // extern "C"
 
 // ======================================================================= host layer

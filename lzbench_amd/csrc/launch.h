@@ -154,6 +154,19 @@ hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* i
                                    uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, const LzhCompactLayout& L,
                                    hipStream_t s);
 
+// the compact layout of a ragged zstd compression (zstd_ragged_compact_hip.hip, zstd_ragged_slots.h): the layout
+// struct above with the record fields carrying the scratch slots -- chunk i's scratch slot is rec_sz[i] bytes at
+// rec_off[i] of a scratch region of rec_cap bytes.  lzh_launch_zstd_compact fills the four arrays (the zstd
+// slot-size kernel, then lzh_launch_scan twice) and runs the match / entropy pair per block index, every launch on
+// s; lzh_launch_pack_compact above packs.  A chunk larger than max_bytes, or one with a slot that ends past its
+// region, gets csizes[i] = 0.  The two host functions are the slot arithmetic for api.cpp (sizing, host mirror).
+struct LzhZstdCompactRegions { uint64_t stage, scratch; };
+LzhZstdCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks);
+void lzh_zstd_compact_slot(int level, uint64_t n, uint64_t* stage_bytes, uint64_t* scratch_bytes);
+hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
+                                   uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
+                                   const LzhCompactLayout& L, hipStream_t s);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

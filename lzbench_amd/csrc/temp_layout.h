@@ -118,6 +118,31 @@ static inline CompactTemp compact_temp(int codec, size_t total_in, size_t max_by
     return t;
 }
 
+// ---- ragged zstd compression, compact layout: every chunk's slots sized from its own size and the call's level
+// (zstd_ragged_slots.h; the uniform-slot chunk_temp takes the worst of four levels):
+//   staging region | scratch region (the two zstd kernels' per-frame areas)
+//   | staging-slot sizes | scratch-slot sizes (u32 each) | staging-slot offsets | scratch-slot offsets
+//   (nchunks + 1 u64 each, scanned on the device)
+// The regions keep chunk_temp's spare 256 bytes; the arrays follow without one, so the total never passes
+// chunk_temp's for the same nchunks and max_bytes by more than the four arrays.
+struct ZstdCompactTemp {
+    LzhZstdCompactRegions reg;
+    size_t stage, scratch, stage_sz, scratch_sz, stage_off, scratch_off, total;
+};
+static inline ZstdCompactTemp zstd_compact_temp(int level, size_t total_in, size_t max_bytes, size_t nchunks) {
+    ZstdCompactTemp t;
+    TempCursor c;
+    t.reg = lzh_zstd_compact_regions(level, total_in, max_bytes, nchunks);
+    t.stage = c.take(t.reg.stage, kGap);
+    t.scratch = c.take(t.reg.scratch, kGap);
+    t.stage_sz = c.take(nchunks * 4);
+    t.scratch_sz = c.take(nchunks * 4);
+    t.stage_off = c.take((nchunks + 1) * 8);
+    t.scratch_off = c.take((nchunks + 1) * 8);
+    t.total = c.at;
+    return t;
+}
+
 // ---- decompression: the scanned offsets (k + 1 u64, used when the caller passes none), then
 //   frames: maxbpf block descriptors per frame (32 bytes each) | block statuses | frame statuses
 //   zstd, snappy: the temp of the split decoder (decode_hip.hip carves it), where there is one

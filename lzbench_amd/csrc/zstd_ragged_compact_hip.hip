@@ -1,0 +1,145 @@
+// lzbench_amd/csrc/zstd_ragged_compact_hip.hip -- the compact compress layout of ragged zstd batches
+// (include/lzbench_hip.h 3c, lzh_zstd_compress_ragged_compact_async): the entry points of zstd_ragged_hip.hip with
+// every chunk's staging slot and scratch slot sized from the chunk's own size and level (zstd_ragged_slots.h) and
+// placed by an exclusive scan, so a batch's temp grows with its total bytes and not with nchunks x the slots of
+// its largest chunk.
+//
+//   lzh_zstd_compact_slots_kernel   chunk i's two slot sizes (u32; 0 for a chunk over max_bytes)
+//   lzh_launch_scan (twice)         the slots' offsets inside the staging region and the scratch region
+//   match / entropy per block       as in zstd_ragged_hip.hip, slots reached through those offsets and sizes
+//   pack                            lzh_pack_compact_kernel (ragged_compact_hip.hip), the layout's record fields
+//                                   carrying the scratch slots
+//
+// A chunk is processed exactly when its size is at most max_bytes and both of its slots end inside their
+// regions (zcompact_span below; the host sizes the regions for the promised total, api.cpp).  Any other chunk is
+// handled as an oversize chunk of zstd_ragged_hip.hip: csizes[i] = 0, no packed bytes, no kernel touches a slot.
+//
+// The kernel bodies are the uniform kernels' text (zstdc_match_body.inc, zstdc_entropy_body.inc), unchanged.  They
+// name a frame's scratch `scratch + f * fstride`, its staging slot `stage + f * stride` of `stride` bytes, and
+// the areas inside the scratch by seq_off .. tab_off.  Here fstride and stride are ZSlot values -- f * slot is the
+// slot's scanned offset, the slot converted to an integer its own size -- and the five offsets are locals laid
+// out for the chunk's own parameters (lzh_zslot_layout: the layout whose stride is the slot's size), where the
+// uniform-slot kernels get them as arguments computed for max_bytes.  Every buffer descriptor the bodies build is
+// therefore bounded by the chunk's own slot.  chunk_size (the batch's max_bytes) and lds_arg still select the
+// hash-table kind alone: speed, never bytes.
+// As in zstd_ragged_hip.hip, zstdc_hip.hip is included for its device functions alone and compiled with its flags.
+#define LZH_DEVICE_FUNCTIONS_ONLY 1
+#include "zstdc_hip.hip"
+#include "zstd_ragged_slots.h"
+
+struct ZSlot {
+    uint64_t off;     // from the region's base (a multiple of 256)
+    uint32_t bytes;
+    // (the bodies pass a slot where they mean its size: `out.init(stage + f * stride, stride)`)
+    __device__ __forceinline__ operator uint64_t() const { return bytes; }
+};
+__device__ __forceinline__ uint64_t operator*(uint64_t, ZSlot s) { return s.off; }
+
+// Chunk i of a compact batch: ragged_span's pointer and size and the chunk's two slots, loaded once and
+// wave-uniform.  false = not processed (over max_bytes, or a slot that ends past its region).
+__device__ __forceinline__ bool zcompact_span(const void* const* ptrs, const uint64_t* bytes, uint64_t i,
+                                              uint64_t max_bytes, const LzhCompactLayout& C, const uint8_t*& p, int& n,
+                                              ZSlot& stage_slot, ZSlot& scratch_slot) {
+    if (!ragged_span(ptrs, bytes, i, max_bytes, p, n)) return false;
+    stage_slot.off = uni64(C.stage_off[i]);
+    stage_slot.bytes = uni(C.stage_sz[i]);
+    scratch_slot.off = uni64(C.rec_off[i]);
+    scratch_slot.bytes = uni(C.rec_sz[i]);
+    return stage_slot.off + stage_slot.bytes <= C.stage_cap && scratch_slot.off + scratch_slot.bytes <= C.rec_cap;
+}
+
+// -------------------------------------------------------------------------------------- slot sizes
+extern "C" __global__ void __launch_bounds__(256)
+lzh_zstd_compact_slots_kernel(const uint64_t* in_bytes, uint64_t max_bytes, int level, uint32_t* stage_sz,
+                              uint32_t* scratch_sz, uint32_t nchunks) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nchunks) return;
+    const uint64_t b = in_bytes[i];
+    const bool over = b > max_bytes;
+    stage_sz[i] = over ? 0u : (uint32_t)lzh_zslot_stage_bytes(b);
+    scratch_sz[i] = over ? 0u : (uint32_t)lzh_zslot_scratch_bytes(level, b);
+}
+
+// ---------------------------------------------------------------------------- match and entropy
+// one wave per chunk; block k of every chunk (a chunk of fewer blocks returns at once)
+extern "C" __global__ void __launch_bounds__(64)
+lzh_zstd_match_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level, int k,
+                              uint8_t* scratch, uint32_t lds_arg, const LzhCompactLayout C) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t zlds[];
+    const int lane = threadIdx.x;
+    const uint64_t f = blockIdx.x;
+    const uint64_t chunk_size = max_bytes;
+    const uint64_t ioff = 0;
+    const uint8_t* in;
+    int sn;
+    ZSlot stride, fstride;
+    if (!zcompact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) return;
+    const uint64_t nf = (uint64_t)sn;
+    const uint64_t in_readable = nf + 16;
+    const Layout Lo = lzh_zslot_layout(lzh_zslot_params(level, nf));
+    const uint64_t seq_off = Lo.seq_off, lit_off = Lo.lit_off, tab_off = Lo.tab_off;
+#include "zstdc_match_body.inc"
+}
+
+extern "C" __global__ void __launch_bounds__(64)
+lzh_zstd_entropy_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
+                                int k, uint8_t* scratch, uint8_t* stage, uint32_t* csizes, const LzhCompactLayout C) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds_raw[(sizeof(ze::Lds) + 3) / 4];
+    LDSA ze::Lds& L = *(LDSA ze::Lds*)lds_raw;
+    const int lane = threadIdx.x;
+    const uint64_t f = blockIdx.x;
+    const uint64_t ioff = 0;
+    const uint8_t* in;
+    int sn;
+    ZSlot stride, fstride;
+    if (!zcompact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) {
+        if (lane == 0 && k == 0) csizes[f] = 0;
+        return;
+    }
+    const uint64_t nf = (uint64_t)sn;
+    const uint64_t in_readable = nf + 16;
+    const Layout Lo = lzh_zslot_layout(lzh_zslot_params(level, nf));
+    const uint64_t seq_off = Lo.seq_off, lit_off = Lo.lit_off, att_off = Lo.att_off, tmp_off = Lo.tmp_off;
+#include "zstdc_entropy_body.inc"
+}
+
+// ------------------------------------------------------------------------- host side: arithmetic, launcher
+#include <algorithm>
+
+LzhZstdCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
+    return lzh_zslot_regions(level, total, max_bytes, nchunks);
+}
+
+void lzh_zstd_compact_slot(int level, uint64_t n, uint64_t* stage_bytes, uint64_t* scratch_bytes) {
+    *stage_bytes = lzh_zslot_stage_bytes(n);
+    *scratch_bytes = lzh_zslot_scratch_bytes(level, n);
+}
+
+hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
+                                   uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
+                                   const LzhCompactLayout& L, hipStream_t s) {
+    if (nchunks == 0) return hipSuccess;
+    // (the block count and the table's LDS of a batch of empty chunks are those of 1-byte chunks, as in
+    // lzh_launch_zstd_ragged)
+    const uint64_t geo = std::max<uint64_t>(max_bytes, 1);
+    const ZParams PF = params_for(level, geo);
+    if (!PF.ok) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lzh_zstd_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes, max_bytes,
+                       level, L.stage_sz, L.rec_sz, nchunks);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = lzh_launch_scan(L.stage_sz, nchunks, L.stage_off, nullptr, s);
+    if (e != hipSuccess) return e;
+    e = lzh_launch_scan(L.rec_sz, nchunks, L.rec_off, nullptr, s);
+    if (e != hipSuccess) return e;
+    const uint32_t nblocks = (uint32_t)((geo + PF.bsize - 1) / PF.bsize);
+    const uint32_t lds_tab = lzh_zstd_lds_table(level, geo);
+    // (every launch on s, as lzh_launch_zstd_ragged: a captured call has no parallel branches)
+    for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
+        hipLaunchKernelGGL(lzh_zstd_match_compact_kernel, dim3(nchunks), dim3(64), lds_tab, s, in_ptrs, in_bytes,
+                           max_bytes, level, (int)k, scratch, lds_tab, L);
+        hipLaunchKernelGGL(lzh_zstd_entropy_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
+                           level, (int)k, scratch, stage, csizes, L);
+    }
+    return hipGetLastError();
+}
