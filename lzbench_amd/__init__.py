@@ -427,20 +427,24 @@ class RaggedCodec:
         if split_decode and not self.zstd:
             raise ValueError("ragged batches: split_decode is a zstd option")
         self.split_decode = split_decode
+        # the variant, chosen once: the compress and decompress calls (their names go into the error texts), each with
+        # the arguments it takes before the chunk arrays, and the sizing call; the compact layouts take the batch's
+        # total too (sizing: after the codec or level; compress: after max_chunk_bytes, and max_total as it is then:
+        # a caller may lower its promise between calls)
+        self._promise = compact or compact_scratch
         if self.zstd:
-            if compact_scratch:
-                ct = L.lzh_zstd_ragged_compact_compress_temp_bytes(self.level, self.max_total, max_chunk_bytes, max_chunks)
-            else:
-                ct = L.lzh_zstd_ragged_compress_temp_bytes(self.level, max_chunk_bytes, max_chunks)
+            self._compress = L.lzh_zstd_compress_ragged_compact_async if compact_scratch else L.lzh_zstd_compress_ragged_async
+            sizing = L.lzh_zstd_ragged_compact_compress_temp_bytes if compact_scratch else L.lzh_zstd_ragged_compress_temp_bytes
+            self._chead, self._decompress, self._dhead = (self.level,), L.lzh_zstd_decompress_ragged_async, ()
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
             if split_decode:   # (0: no split decoder for chunks of this size)
                 dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
-        elif compact:
-            ct = L.lzh_ragged_compact_compress_temp_bytes(self.codec, self.max_total, max_chunk_bytes, max_chunks)
         else:
-            ct = L.lzh_ragged_compress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
-        if not self.zstd:
+            self._compress = L.lzh_compress_ragged_compact_async if compact else L.lzh_compress_ragged_async
+            sizing = L.lzh_ragged_compact_compress_temp_bytes if compact else L.lzh_ragged_compress_temp_bytes
+            self._chead, self._decompress, self._dhead = (self.codec, self.level), L.lzh_decompress_ragged_async, (self.codec,)
             dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
+        ct = sizing(self._chead[0], *((self.max_total,) if self._promise else ()), max_chunk_bytes, max_chunks)
         if ct == 0 or dt == 0:
             raise ValueError(f"ragged batches: codec {codec} (level {self.level}) / chunks of {max_chunk_bytes} bytes "
                              "are not supported")
@@ -485,24 +489,11 @@ class RaggedCodec:
         copy, so the call can be captured in a graph."""
         self._in = d   # (kept alive until the next call: the kernels read it asynchronously)
         self.k = k
-        out = (self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
-               self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
-        if self.zstd and self.compact_scratch:
-            rc = lib().lzh_zstd_compress_ragged_compact_async(self.level, d[0].data_ptr(), d[1].data_ptr(), k,
-                                                              self.max_chunk_bytes, self.max_total, *out)
-        elif self.zstd:
-            rc = lib().lzh_zstd_compress_ragged_async(self.level, d[0].data_ptr(), d[1].data_ptr(), k,
-                                                      self.max_chunk_bytes, *out)
-        elif self.compact:
-            rc = lib().lzh_compress_ragged_compact_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
-                                                         self.max_chunk_bytes, self.max_total, *out)
-        else:
-            rc = lib().lzh_compress_ragged_async(self.codec, self.level, d[0].data_ptr(), d[1].data_ptr(), k,
-                                                 self.max_chunk_bytes, *out)
+        rc = self._compress(*self._chead, d[0].data_ptr(), d[1].data_ptr(), k, self.max_chunk_bytes,
+                            *((self.max_total,) if self._promise else ()), self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
+                            self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
         if rc:
-            name = (f"lzh_zstd_compress_ragged{'_compact' if self.compact_scratch else ''}" if self.zstd
-                    else f"lzh_compress_ragged{'_compact' if self.compact else ''}")
-            raise RuntimeError(f"{name}_async failed ({rc})")
+            raise RuntimeError(f"{self._compress.__name__} failed ({rc})")
 
     def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:
         """Decode chunk i to out_buf[out_offsets[i] : out_offsets[i] + out_sizes[i]]; self.status[i] = its
@@ -518,15 +509,12 @@ class RaggedCodec:
         csizes = self.csizes if csizes is None else csizes
         self._out = d
         self.k = k
-        args = (packed.data_ptr(), packed.numel(), csizes.data_ptr(), offsets.data_ptr() if offsets is not None else None,
-                d[0].data_ptr(), d[1].data_ptr(), k, self.max_chunk_bytes, self.status.data_ptr(), self.dtemp.data_ptr(),
-                self.dtemp.numel(), self._stream())
-        if self.zstd:
-            rc = lib().lzh_zstd_decompress_ragged_async(*args)
-        else:
-            rc = lib().lzh_decompress_ragged_async(self.codec, *args)
+        rc = self._decompress(*self._dhead, packed.data_ptr(), packed.numel(), csizes.data_ptr(),
+                              offsets.data_ptr() if offsets is not None else None, d[0].data_ptr(), d[1].data_ptr(), k,
+                              self.max_chunk_bytes, self.status.data_ptr(), self.dtemp.data_ptr(), self.dtemp.numel(),
+                              self._stream())
         if rc:
-            raise RuntimeError(f"lzh_{'zstd_' if self.zstd else ''}decompress_ragged_async failed ({rc})")
+            raise RuntimeError(f"{self._decompress.__name__} failed ({rc})")
 
     def packed_total(self) -> int:
         return int(self.offsets[self.k].item())

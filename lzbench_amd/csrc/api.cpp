@@ -316,55 +316,38 @@ size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchu
     return total_in_bytes + var + nchunks * (codec_bound(codec, 0) + 8) + 64;
 }
 
-// the argument checks of the two ragged compress calls, in their order: an error, 1 for an empty batch (nothing to
-// do: LZH_OK), 0 to go on.  (The grid limit comes before the caller's temp check.)
-static int ragged_compress_args(int codec, size_t nchunks, size_t max_chunk_bytes, bool pointers) {
-    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
-    if (nchunks == 0) return 1;
-    if (!pointers) return LZH_EARG;
-    if (nchunks * (size_t)lzh_snappy_ragged_frags(max_chunk_bytes) > 0x7fffffffu) return LZH_EARG;   // launch grids
-    return 0;
-}
+}  // extern "C"
 
-int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
-                              size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
-                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
-                              void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const bool ptrs = d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp;
-    if (const int rc = ragged_compress_args(codec, nchunks, max_chunk_bytes, ptrs)) return rc < 0 ? rc : LZH_OK;
-    const ChunkTemp t = chunk_temp(codec, nchunks, max_chunk_bytes);
-    if (temp_bytes < t.total) return LZH_ESPACE;
-    const uint32_t k = (uint32_t)nchunks;
-    const size_t stride = t.stride;
-    uint8_t* base = (uint8_t*)d_temp;
-    uint8_t* stage = base + t.stage;
-    uint8_t* recs = base + t.recs;
-    uint32_t* hdr = (uint32_t*)(base + t.hdr);
+// The four ragged compress calls (3b, 3c; uniform slots, compact layout): the argument checks in their order (ok: the
+// codec / level takes max_chunk_bytes; grid_factor: launch blocks per chunk; temp_need: the layout's total), then
+// compress() -> scan -> pack(), the two callables enqueueing on s and returning HIP's verdict.
+template <class Compress, class Pack>
+static int ragged_compress(bool ok, size_t nchunks, bool pointers, size_t grid_factor, size_t temp_need,
+                           size_t temp_bytes, const uint32_t* d_csizes, uint64_t* d_offsets, hipStream_t s,
+                           Compress compress, Pack pack) {
+    if (!ok) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!pointers) return LZH_EARG;
+    if (nchunks * grid_factor > 0x7fffffffu) return LZH_EARG;   // launch grids
+    if (temp_bytes < temp_need) return LZH_ESPACE;
     {
         Range range("lzh:compress_kernel");
-        if (codec == LZH_CODEC_LZ4)
-            LZH_CHECK(lzh_launch_lz4_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level, stage, stride,
-                                            d_csizes, k, recs, t.rec_stride, hdr, s));
-        else
-            LZH_CHECK(lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, k, recs,
-                                               t.rec_stride, hdr, s));
+        LZH_CHECK(compress());
     }
     Range range("lzh:scan_pack");
     LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, stride, d_csizes, d_offsets,
-                                     (uint8_t*)d_packed, packed_cap, k, s));
+    LZH_CHECK(pack());
     return LZH_OK;
 }
 
-int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
-                                const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
-                                size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
-                                size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
+// The two ragged decompress calls: the argument checks in their order, the temp of ragged_decode_temp, then
+// decode(offs, t) with the caller's offsets or, without them, the ones scanned into temp.
+template <class Decode>
+static int ragged_decompress(bool ok, size_t nchunks, bool pointers, const uint32_t* d_csizes, const uint64_t* d_offsets,
+                             void* d_temp, size_t temp_bytes, hipStream_t s, Decode decode) {
+    if (!ok) return LZH_EARG;
     if (nchunks == 0) return LZH_OK;
-    if (!d_packed || !d_csizes || !d_out_ptrs || !d_out_bytes || !d_status || !d_temp) return LZH_EARG;
+    if (!pointers) return LZH_EARG;
     if (nchunks > 0x7fffffffu) return LZH_EARG;
     const DecodeTemp t = ragged_decode_temp(nchunks);
     if (temp_bytes < t.total) return LZH_ESPACE;
@@ -374,13 +357,84 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
         LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)((uint8_t*)d_temp + t.scan), nullptr, s));
         offs = (const uint64_t*)((uint8_t*)d_temp + t.scan);
     }
-    void* desc = (uint8_t*)d_temp + t.desc;
-    LZH_CHECK(lzh_launch_ragged_desc(offs, d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes, desc, d_status,
-                                     (uint32_t)nchunks, s));
-    // (the block decoder adds the descriptor's destination, the chunk's address, to a null output base)
-    LZH_CHECK(lzh_launch_decompress(codec, (const uint8_t*)d_packed, packed_readable, nullptr, nullptr, 0, 0, nullptr,
-                                    d_status, (uint32_t)nchunks, s, desc));
+    LZH_CHECK(decode(offs, t));
     return LZH_OK;
+}
+
+// The debug calls of the two compact layouts: the two regions (zstd: recs = scratch), and the host mirror of the
+// slot placement (the slot-size kernel, the two scans, compact_span; slot(n): a chunk's two slot sizes)
+static int compact_regions_out(bool ok, const CompactTemp& t, uint64_t* out) {
+    if (!ok || !out) return LZH_EARG;
+    out[0] = t.stage;
+    out[1] = t.reg.stage;
+    out[2] = t.recs;
+    out[3] = t.reg.recs;
+    return LZH_OK;
+}
+
+template <class Slot>
+static int compact_slots_mirror(bool ok, const LzhCompactRegions& reg, const uint64_t* sizes, size_t nchunks,
+                                size_t max_chunk_bytes, uint64_t* stage_off, uint64_t* rec_off, uint8_t* processed,
+                                Slot slot) {
+    if (!ok) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!sizes || !stage_off || !rec_off || !processed) return LZH_EARG;
+    uint64_t so = 0, ro = 0;
+    for (size_t i = 0; i < nchunks; i++) {
+        const bool over = sizes[i] > max_chunk_bytes;
+        const LzhCompactRegions sz = over ? LzhCompactRegions{0, 0} : slot(sizes[i]);
+        stage_off[i] = so;
+        rec_off[i] = ro;
+        processed[i] = !over && so + sz.stage <= reg.stage && ro + sz.recs <= reg.recs;
+        so += sz.stage;
+        ro += sz.recs;
+    }
+    return LZH_OK;
+}
+
+extern "C" {
+
+int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                              size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                              void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const ChunkTemp t = chunk_temp(codec, nchunks, max_chunk_bytes);
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;   // (null until ragged_compress has checked it: offsets are added after that)
+    return ragged_compress(
+        ragged_ok(codec, max_chunk_bytes), nchunks, d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp,
+        lzh_snappy_ragged_frags(max_chunk_bytes), t.total, temp_bytes, d_csizes, d_offsets, s,
+        [&] {
+            return codec == LZH_CODEC_LZ4
+                       ? lzh_launch_lz4_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level,
+                                               base + t.stage, t.stride, d_csizes, k, base + t.recs, t.rec_stride,
+                                               (uint32_t*)(base + t.hdr), s)
+                       : lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride,
+                                                  d_csizes, k, base + t.recs, t.rec_stride, (uint32_t*)(base + t.hdr), s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
+}
+
+int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return ragged_decompress(
+        ragged_ok(codec, max_chunk_bytes), nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
+        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp& t) {
+            void* desc = (uint8_t*)d_temp + t.desc;
+            const hipError_t e = lzh_launch_ragged_desc(offs, d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes, desc,
+                                                        d_status, (uint32_t)nchunks, s);
+            if (e != hipSuccess) return e;
+            // (the block decoder adds the descriptor's destination, the chunk's address, to a null output base)
+            return lzh_launch_decompress(codec, (const uint8_t*)d_packed, packed_readable, nullptr, nullptr, 0, 0, nullptr,
+                                         d_status, (uint32_t)nchunks, s, desc);
+        });
 }
 
 // ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
@@ -433,24 +487,21 @@ int lzh_zstd_compress_ragged_async(int level, const void* const* d_in_ptrs, cons
                                    size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
                                    uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
-    if (nchunks > 0x7fffffffu) return LZH_EARG;   // launch grids
     const ChunkTemp t = zstd_ragged_temp(nchunks, max_chunk_bytes);
-    if (temp_bytes < t.total) return LZH_ESPACE;
     const uint32_t k = (uint32_t)nchunks;
     uint8_t* base = (uint8_t*)d_temp;
-    {
-        Range range("lzh:compress_kernel");
-        LZH_CHECK(lzh_launch_zstd_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes,
-                                         k, base + t.recs, t.rec_stride, s));
-    }
-    Range range("lzh:scan_pack");
-    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                     d_offsets, (uint8_t*)d_packed, packed_cap, k, s));
-    return LZH_OK;
+    return ragged_compress(
+        zstd_ragged_ok(level, max_chunk_bytes), nchunks,
+        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
+        d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes,
+                                          k, base + t.recs, t.rec_stride, s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
 }
 
 int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
@@ -458,37 +509,27 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
                                      size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
                                      size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (max_chunk_bytes > kLz4SplitMax) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!d_packed || !d_csizes || !d_out_ptrs || !d_out_bytes || !d_status || !d_temp) return LZH_EARG;
-    if (nchunks > 0x7fffffffu) return LZH_EARG;
-    const DecodeTemp t = ragged_decode_temp(nchunks);
-    if (temp_bytes < t.total) return LZH_ESPACE;
-    Range range("lzh:decompress");
-    const uint64_t* offs = d_offsets;
-    if (!offs) {
-        LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, (uint64_t*)((uint8_t*)d_temp + t.scan), nullptr, s));
-        offs = (const uint64_t*)((uint8_t*)d_temp + t.scan);
-    }
-    // with room for it the split decoder's layout lives in temp (the offsets at the same place); with less every
-    // frame is decoded whole by one wave
-    const ZstdRaggedSplitTemp z = zstd_ragged_split_temp(nchunks, max_chunk_bytes);
-    uint8_t* base = (uint8_t*)d_temp;
-    if (z.ok && temp_bytes >= z.total) {
-        const LzhZstdSplitTemp split = {base + z.frames, (int32_t*)(base + z.state), base + z.fields,
-                                        (uint32_t*)(base + z.njobs), base + z.jobs};
-        LZH_CHECK(lzh_launch_zstd_decompress_ragged_split((const uint8_t*)d_packed, packed_readable, offs, d_csizes,
-                                                          d_out_ptrs, d_out_bytes, max_chunk_bytes, d_status,
-                                                          (uint32_t)nchunks, split, s));
-        return LZH_OK;
-    }
-    LZH_CHECK(lzh_launch_zstd_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
-                                                d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, s));
-    return LZH_OK;
+    return ragged_decompress(
+        max_chunk_bytes <= kLz4SplitMax, nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
+        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+            // with room for it the split decoder's layout lives in temp (the offsets at the same place); with less
+            // every frame is decoded whole by one wave
+            const ZstdRaggedSplitTemp z = zstd_ragged_split_temp(nchunks, max_chunk_bytes);
+            uint8_t* base = (uint8_t*)d_temp;
+            if (z.ok && temp_bytes >= z.total) {
+                const LzhZstdSplitTemp split = {base + z.frames, (int32_t*)(base + z.state), base + z.fields,
+                                                (uint32_t*)(base + z.njobs), base + z.jobs};
+                return lzh_launch_zstd_decompress_ragged_split((const uint8_t*)d_packed, packed_readable, offs, d_csizes,
+                                                               d_out_ptrs, d_out_bytes, max_chunk_bytes, d_status,
+                                                               (uint32_t)nchunks, split, s);
+            }
+            return lzh_launch_zstd_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
+                                                     d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, s);
+        });
 }
 
 // ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h); compact_temp
-// lays the temp out for the sizing call, the async call and the host mirror ----
+// lays the temp out for the sizing call, the async call and the debug calls ----
 size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks) {
     if (!ragged_ok(codec, max_chunk_bytes)) return 0;
     return compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks).total;
@@ -496,33 +537,18 @@ size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, 
 
 int lzh_debug_ragged_compact_regions(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                      uint64_t* out) {
-    if (!ragged_ok(codec, max_chunk_bytes) || !out) return LZH_EARG;
-    const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
-    out[0] = 0;
-    out[1] = t.reg.stage;
-    out[2] = t.recs;
-    out[3] = t.reg.recs;
-    return LZH_OK;
+    return compact_regions_out(ragged_ok(codec, max_chunk_bytes),
+                               compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks), out);
 }
 
 int lzh_debug_ragged_compact_slots(int codec, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
                                    size_t total_in_bytes, uint64_t* stage_off, uint64_t* rec_off, uint8_t* processed) {
-    if (!ragged_ok(codec, max_chunk_bytes)) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!sizes || !stage_off || !rec_off || !processed) return LZH_EARG;
-    const LzhCompactRegions reg = lzh_compact_regions(codec, total_in_bytes, max_chunk_bytes, nchunks);
-    uint64_t so = 0, ro = 0;
-    for (size_t i = 0; i < nchunks; i++) {   // lzh_compact_slots_kernel, the two scans, compact_span
-        const bool over = sizes[i] > max_chunk_bytes;
-        const uint64_t ss = over ? 0 : lzh_slot_stage_bytes(codec, sizes[i]);
-        const uint64_t rs = over ? 0 : lzh_slot_rec_bytes(codec, sizes[i], max_chunk_bytes > 65536);
-        stage_off[i] = so;
-        rec_off[i] = ro;
-        processed[i] = !over && so + ss <= reg.stage && ro + rs <= reg.recs;
-        so += ss;
-        ro += rs;
-    }
-    return LZH_OK;
+    return compact_slots_mirror(ragged_ok(codec, max_chunk_bytes),
+                                lzh_compact_regions(codec, total_in_bytes, max_chunk_bytes, nchunks), sizes, nchunks,
+                                max_chunk_bytes, stage_off, rec_off, processed, [&](uint64_t n) {
+                                    return LzhCompactRegions{lzh_slot_stage_bytes(codec, n),
+                                                             lzh_slot_rec_bytes(codec, n, max_chunk_bytes > 65536)};
+                                });
 }
 
 int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
@@ -530,31 +556,26 @@ int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d
                                       size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp,
                                       size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool ptrs = d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp;
-    if (const int rc = ragged_compress_args(codec, nchunks, max_chunk_bytes, ptrs)) return rc < 0 ? rc : LZH_OK;
     const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
-    if (temp_bytes < t.total) return LZH_ESPACE;
     const uint32_t k = (uint32_t)nchunks;
     uint8_t* base = (uint8_t*)d_temp;
-    uint8_t* stage = base + t.stage;
-    uint8_t* recs = base + t.recs;
-    uint32_t* hdr = (uint32_t*)(base + t.hdr);
-    const LzhCompactLayout L = {(uint32_t*)(base + t.stage_sz), (uint32_t*)(base + t.rec_sz),
-                                (uint64_t*)(base + t.stage_off), (uint64_t*)(base + t.rec_off), t.reg.stage, t.reg.recs};
-    {
-        Range range("lzh:compress_kernel");
-        LZH_CHECK(lzh_launch_compact_slots(codec, d_in_bytes, max_chunk_bytes, L, k, s));
-        if (codec == LZH_CODEC_LZ4)
-            LZH_CHECK(lzh_launch_lz4_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level, stage, d_csizes,
-                                             k, recs, hdr, L, s));
-        else
-            LZH_CHECK(lzh_launch_snappy_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, d_csizes, k, recs, hdr, L, s));
-    }
-    Range range("lzh:scan_pack");
-    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, stage, d_csizes, d_offsets,
-                                      (uint8_t*)d_packed, packed_cap, k, L, s));
-    return LZH_OK;
+    return ragged_compress(
+        ragged_ok(codec, max_chunk_bytes), nchunks, d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp,
+        lzh_snappy_ragged_frags(max_chunk_bytes), t.total, temp_bytes, d_csizes, d_offsets, s,
+        [&] {
+            const LzhCompactLayout L = t.layout(base);
+            const hipError_t e = lzh_launch_compact_slots(codec, d_in_bytes, max_chunk_bytes, L, k, s);
+            if (e != hipSuccess) return e;
+            return codec == LZH_CODEC_LZ4
+                       ? lzh_launch_lz4_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level,
+                                                base + t.stage, d_csizes, k, base + t.recs, (uint32_t*)(base + t.hdr), L, s)
+                       : lzh_launch_snappy_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, k,
+                                                   base + t.recs, (uint32_t*)(base + t.hdr), L, s);
+        },
+        [&] {
+            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
+                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
+        });
 }
 
 // ---- 3c, compact compress layout: every chunk's staging slot and scratch slot sized from its own size and the
@@ -568,34 +589,17 @@ size_t lzh_zstd_ragged_compact_compress_temp_bytes(int level, size_t total_in_by
 
 int lzh_debug_zstd_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                           uint64_t* out) {
-    if (!zstd_ragged_ok(level, max_chunk_bytes) || !out) return LZH_EARG;
-    const ZstdCompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
-    out[0] = t.stage;
-    out[1] = t.reg.stage;
-    out[2] = t.scratch;
-    out[3] = t.reg.scratch;
-    return LZH_OK;
+    return compact_regions_out(zstd_ragged_ok(level, max_chunk_bytes),
+                               zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks), out);
 }
 
 int lzh_debug_zstd_ragged_compact_slots(int level, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
                                         size_t total_in_bytes, uint64_t* stage_off, uint64_t* scratch_off,
                                         uint8_t* processed) {
-    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!sizes || !stage_off || !scratch_off || !processed) return LZH_EARG;
-    const LzhZstdCompactRegions reg = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks).reg;
-    uint64_t so = 0, co = 0;
-    for (size_t i = 0; i < nchunks; i++) {   // lzh_zstd_compact_slots_kernel, the two scans, zcompact_span
-        const bool over = sizes[i] > max_chunk_bytes;
-        uint64_t ss = 0, cs = 0;
-        if (!over) lzh_zstd_compact_slot(level, sizes[i], &ss, &cs);
-        stage_off[i] = so;
-        scratch_off[i] = co;
-        processed[i] = !over && so + ss <= reg.stage && co + cs <= reg.scratch;
-        so += ss;
-        co += cs;
-    }
-    return LZH_OK;
+    return compact_slots_mirror(zstd_ragged_ok(level, max_chunk_bytes),
+                                lzh_zstd_compact_regions(level, total_in_bytes, max_chunk_bytes, nchunks), sizes, nchunks,
+                                max_chunk_bytes, stage_off, scratch_off, processed,
+                                [&](uint64_t n) { return lzh_zstd_compact_slot(level, n); });
 }
 
 int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
@@ -603,28 +607,22 @@ int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_pt
                                            void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
                                            void* d_temp, size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    if (!zstd_ragged_ok(level, max_chunk_bytes)) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!d_in_ptrs || !d_in_bytes || !d_packed || !d_csizes || !d_offsets || !d_temp) return LZH_EARG;
-    if (nchunks > 0x7fffffffu) return LZH_EARG;   // launch grids
-    const ZstdCompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
-    if (temp_bytes < t.total) return LZH_ESPACE;
+    const CompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
     const uint32_t k = (uint32_t)nchunks;
     uint8_t* base = (uint8_t*)d_temp;
     // (the layout's record fields carry the scratch slots: the pack kernel's lookup is the LZ4 / snappy one)
-    const LzhCompactLayout L = {(uint32_t*)(base + t.stage_sz), (uint32_t*)(base + t.scratch_sz),
-                                (uint64_t*)(base + t.stage_off), (uint64_t*)(base + t.scratch_off), t.reg.stage,
-                                t.reg.scratch};
-    {
-        Range range("lzh:compress_kernel");
-        LZH_CHECK(lzh_launch_zstd_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes, k,
-                                          base + t.scratch, L, s));
-    }
-    Range range("lzh:scan_pack");
-    LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
-                                      (uint8_t*)d_packed, packed_cap, k, L, s));
-    return LZH_OK;
+    return ragged_compress(
+        zstd_ragged_ok(level, max_chunk_bytes), nchunks,
+        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
+        d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes, k,
+                                           base + t.recs, t.layout(base), s);
+        },
+        [&] {
+            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
+                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
+        });
 }
 
 }  // extern "C"

@@ -130,7 +130,8 @@ hipError_t lzh_launch_ragged_desc(const uint64_t* offsets, const uint32_t* csize
 // the compact layout of a ragged compression (ragged_compact_hip.hip, ragged_slots.h): chunk i's staging slot is
 // stage_sz[i] bytes at stage_off[i] of a staging region of stage_cap bytes, its record slot rec_sz[i] bytes at
 // rec_off[i] of a record region of rec_cap bytes (device arrays: nchunks u32, nchunks + 1 u64).
-// lzh_launch_compact_slots fills the four arrays (the slot-size kernel, then lzh_launch_scan twice); the other
+// lzh_launch_compact_slots fills the four arrays (the slot-size kernel, then lzh_launch_compact_scans: the offset
+// arrays from the size arrays, lzh_launch_scan twice); the other
 // launchers are the ragged ones above with the slots looked up there; hdr: the per-chunk record counts.  A chunk
 // larger than max_bytes, or one with a slot that ends past its region, gets csizes[i] = 0.
 // (the arrays are written by lzh_launch_compact_slots alone; every other kernel takes the struct as const)
@@ -141,6 +142,7 @@ struct LzhCompactLayout {
     uint64_t* rec_off;
     uint64_t stage_cap, rec_cap;
 };
+hipError_t lzh_launch_compact_scans(const LzhCompactLayout& L, uint32_t nchunks, hipStream_t s);
 hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,
                                     uint32_t nchunks, hipStream_t s);
 hipError_t lzh_launch_lz4_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
@@ -157,12 +159,13 @@ hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* i
 // the compact layout of a ragged zstd compression (zstd_ragged_compact_hip.hip, zstd_ragged_slots.h): the layout
 // struct above with the record fields carrying the scratch slots -- chunk i's scratch slot is rec_sz[i] bytes at
 // rec_off[i] of a scratch region of rec_cap bytes.  lzh_launch_zstd_compact fills the four arrays (the zstd
-// slot-size kernel, then lzh_launch_scan twice) and runs the match / entropy pair per block index, every launch on
+// slot-size kernel, then lzh_launch_compact_scans) and runs the match / entropy pair per block index, every launch on
 // s; lzh_launch_pack_compact above packs.  A chunk larger than max_bytes, or one with a slot that ends past its
-// region, gets csizes[i] = 0.  The two host functions are the slot arithmetic for api.cpp (sizing, host mirror).
-struct LzhZstdCompactRegions { uint64_t stage, scratch; };
-LzhZstdCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks);
-void lzh_zstd_compact_slot(int level, uint64_t n, uint64_t* stage_bytes, uint64_t* scratch_bytes);
+// region, gets csizes[i] = 0.  The two host functions are the slot arithmetic for api.cpp (sizing, host mirror):
+// the two regions, and the two slots of a chunk of n bytes, each as {staging bytes, scratch bytes}.
+struct LzhCompactRegions;   // ragged_slots.h
+LzhCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks);
+LzhCompactRegions lzh_zstd_compact_slot(int level, uint64_t n);
 hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
                                    uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
                                    const LzhCompactLayout& L, hipStream_t s);

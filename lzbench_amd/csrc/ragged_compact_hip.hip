@@ -8,13 +8,13 @@
 //   parse / emit / pack        as in ragged_hip.hip, slots reached through those offsets and sizes
 //
 // A chunk is processed exactly when its size is at most max_bytes and both of its slots end inside their
-// regions (compact_span below; the host sizes the regions for the promised total, api.cpp).  Any other chunk is
+// regions (compact_span, ragged_slots.h; the host sizes the regions for the promised total, api.cpp).  Any other chunk is
 // handled as an oversize chunk of ragged_hip.hip: csizes[i] = 0, no packed bytes, no kernel touches a slot.
 //
 // The kernel bodies are the uniform kernels' text (*_body.inc), which names a slot `recs + chunk * rec_stride`
 // of `(uint32_t)rec_stride` bytes (and `stage + chunk * stride`).  That text stays as it is -- moving the
 // expression changes the uniform kernels' schedule and with it their code hashes -- so here rec_stride and
-// stride are CompactSlot values: chunk * slot is the slot's scanned offset, an explicit cast of it to an integer
+// stride are CompactSlot values (ragged_slots.h): chunk * slot is the slot's scanned offset, an explicit cast of it to an integer
 // type the slot's own size (the two forms the bodies use; nothing else compiles).  The buffer descriptors the bodies build are therefore bounded by the chunk's own slot.
 // As in ragged_hip.hip the two codec files are included for their device functions alone.
 #define LZH_DEVICE_FUNCTIONS_ONLY 1
@@ -24,29 +24,6 @@
 #include "ragged_slots.h"
 
 static_assert(kLzhSnFragRecBytes == (uint64_t)kFragRecs * 8, "ragged_slots.h: the snappy fragment's record stride");
-
-struct CompactSlot {
-    uint64_t off;     // from the region's base (a multiple of 256)
-    uint32_t bytes;
-    // (explicit: only the bodies' casts `(uint32_t)stride` / `(uint64_t)stride` read the size; any other arithmetic
-    // on a slot, or passing one where an integer is expected, does not compile)
-    __device__ __forceinline__ explicit operator uint32_t() const { return bytes; }
-    __device__ __forceinline__ explicit operator uint64_t() const { return bytes; }
-};
-__device__ __forceinline__ uint64_t operator*(uint64_t, CompactSlot s) { return s.off; }
-
-// Chunk i of a compact batch: ragged_span's pointer and size and the chunk's two slots, loaded once and
-// wave-uniform.  false = not processed (over max_bytes, or a slot that ends past its region).
-__device__ __forceinline__ bool compact_span(const void* const* ptrs, const uint64_t* bytes, uint64_t i,
-                                             uint64_t max_bytes, const LzhCompactLayout& L, const uint8_t*& p, int& n,
-                                             CompactSlot& stage_slot, CompactSlot& rec_slot) {
-    if (!ragged_span(ptrs, bytes, i, max_bytes, p, n)) return false;
-    stage_slot.off = uni64(L.stage_off[i]);
-    stage_slot.bytes = uni(L.stage_sz[i]);
-    rec_slot.off = uni64(L.rec_off[i]);
-    rec_slot.bytes = uni(L.rec_sz[i]);
-    return stage_slot.off + stage_slot.bytes <= L.stage_cap && rec_slot.off + rec_slot.bytes <= L.rec_cap;
-}
 
 // -------------------------------------------------------------------------------------- slot sizes
 extern "C" __global__ void __launch_bounds__(256)
@@ -178,16 +155,18 @@ lzh_pack_compact_kernel(const void* const* in_ptrs, const uint64_t* in_bytes, ui
 }
 
 // ------------------------------------------------------------------------------------ launchers
+hipError_t lzh_launch_compact_scans(const LzhCompactLayout& L, uint32_t nchunks, hipStream_t s) {
+    const hipError_t e = lzh_launch_scan(L.stage_sz, nchunks, L.stage_off, nullptr, s);
+    return e != hipSuccess ? e : lzh_launch_scan(L.rec_sz, nchunks, L.rec_off, nullptr, s);
+}
+
 hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,
                                     uint32_t nchunks, hipStream_t s) {
     if (nchunks == 0) return hipSuccess;
     hipLaunchKernelGGL(lzh_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes, max_bytes, codec,
                        L.stage_sz, L.rec_sz, nchunks);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = lzh_launch_scan(L.stage_sz, nchunks, L.stage_off, nullptr, s);
-    if (e != hipSuccess) return e;
-    return lzh_launch_scan(L.rec_sz, nchunks, L.rec_off, nullptr, s);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : lzh_launch_compact_scans(L, nchunks, s);
 }
 
 hipError_t lzh_launch_lz4_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,

@@ -62,3 +62,33 @@ LZH_HD LzhCompactRegions lzh_compact_regions(int codec, uint64_t total, uint64_t
     r.recs = lzh_slot_align(rc < rc_u ? rc : rc_u);
     return r;
 }
+
+// ---- device side, for the two compact translation units (ragged_compact_hip.hip, zstd_ragged_compact_hip.hip;
+// after common.h, whose LZH_WAVE is the guard: api.cpp includes this file for the arithmetic above alone) ----
+#ifdef LZH_WAVE
+#include "launch.h"
+
+// A chunk's slot, for the bodies' `stride`: chunk * slot is its scanned offset, a conversion to an integer its size
+struct CompactSlot {
+    uint64_t off;     // from the region's base (a multiple of 256)
+    uint32_t bytes;
+    // (explicit: only the bodies' casts `(uint32_t)stride` / `(uint64_t)stride` read the size; any other arithmetic
+    // on a slot, or passing one where an integer is expected, does not compile)
+    __device__ __forceinline__ explicit operator uint32_t() const { return bytes; }
+    __device__ __forceinline__ explicit operator uint64_t() const { return bytes; }
+};
+__device__ __forceinline__ uint64_t operator*(uint64_t, CompactSlot s) { return s.off; }
+
+// Chunk i of a compact batch: ragged_span's pointer and size and the chunk's two slots, loaded once and
+// wave-uniform.  false = not processed (over max_bytes, or a slot that ends past its region).
+__device__ __forceinline__ bool compact_span(const void* const* ptrs, const uint64_t* bytes, uint64_t i,
+                                             uint64_t max_bytes, const LzhCompactLayout& L, const uint8_t*& p, int& n,
+                                             CompactSlot& stage_slot, CompactSlot& rec_slot) {
+    if (!ragged_span(ptrs, bytes, i, max_bytes, p, n)) return false;
+    stage_slot.off = uni64(L.stage_off[i]);
+    stage_slot.bytes = uni(L.stage_sz[i]);
+    rec_slot.off = uni64(L.rec_off[i]);
+    rec_slot.bytes = uni(L.rec_sz[i]);
+    return stage_slot.off + stage_slot.bytes <= L.stage_cap && rec_slot.off + rec_slot.bytes <= L.rec_cap;
+}
+#endif

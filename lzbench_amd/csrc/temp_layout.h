@@ -95,14 +95,31 @@ static inline FrameTemp frame_temp(const FrameGeo& g) {
     return t;
 }
 
-// ---- ragged compression, compact layout: every chunk's slots sized from its own size (ragged_slots.h):
-//   staging region | record region, then the per-chunk record counts (sized for max_bytes as in chunk_temp)
+// ---- ragged compression, compact layout: every chunk's slots sized from its own size (LZ4 / snappy:
+// ragged_slots.h; zstd: its own size and the call's level, zstd_ragged_slots.h, where the uniform-slot chunk_temp
+// takes the worst of four levels):
+//   staging region | record region (zstd: the scratch region, the two zstd kernels' per-frame areas)
+//   | LZ4 / snappy: the per-chunk record counts (sized for max_bytes as in chunk_temp)
 //   | staging-slot sizes | record-slot sizes (u32 each) | staging-slot offsets | record-slot offsets
 //   (nchunks + 1 u64 each, scanned on the device)
+// The spare 256 bytes differ: LZ4 / snappy have none after the records and one after the last array; zstd keeps
+// chunk_temp's after both regions and its arrays follow without one, so its total never passes chunk_temp's for
+// the same nchunks and max_bytes by more than the four arrays.
 struct CompactTemp {
     LzhCompactRegions reg;
     size_t stage, recs, hdr, stage_sz, rec_sz, stage_off, rec_off, total;
+    LzhCompactLayout layout(uint8_t* base) const {
+        return {(uint32_t*)(base + stage_sz), (uint32_t*)(base + rec_sz), (uint64_t*)(base + stage_off),
+                (uint64_t*)(base + rec_off), reg.stage, reg.recs};
+    }
 };
+static inline void compact_arrays(CompactTemp& t, TempCursor& c, size_t nchunks, size_t gap) {
+    t.stage_sz = c.take(nchunks * 4);
+    t.rec_sz = c.take(nchunks * 4);
+    t.stage_off = c.take((nchunks + 1) * 8);
+    t.rec_off = c.take((nchunks + 1) * 8, gap);
+    t.total = c.at;
+}
 static inline CompactTemp compact_temp(int codec, size_t total_in, size_t max_bytes, size_t nchunks) {
     CompactTemp t;
     TempCursor c;
@@ -110,36 +127,16 @@ static inline CompactTemp compact_temp(int codec, size_t total_in, size_t max_by
     t.stage = c.take(t.reg.stage, kGap);
     t.recs = c.take(t.reg.recs);
     t.hdr = c.take(codec == LZH_CODEC_LZ4 ? nchunks * 8 : nchunks * 4 * lzh_snappy_ragged_frags(max_bytes), kGap);
-    t.stage_sz = c.take(nchunks * 4);
-    t.rec_sz = c.take(nchunks * 4);
-    t.stage_off = c.take((nchunks + 1) * 8);
-    t.rec_off = c.take((nchunks + 1) * 8, kGap);
-    t.total = c.at;
+    compact_arrays(t, c, nchunks, kGap);
     return t;
 }
-
-// ---- ragged zstd compression, compact layout: every chunk's slots sized from its own size and the call's level
-// (zstd_ragged_slots.h; the uniform-slot chunk_temp takes the worst of four levels):
-//   staging region | scratch region (the two zstd kernels' per-frame areas)
-//   | staging-slot sizes | scratch-slot sizes (u32 each) | staging-slot offsets | scratch-slot offsets
-//   (nchunks + 1 u64 each, scanned on the device)
-// The regions keep chunk_temp's spare 256 bytes; the arrays follow without one, so the total never passes
-// chunk_temp's for the same nchunks and max_bytes by more than the four arrays.
-struct ZstdCompactTemp {
-    LzhZstdCompactRegions reg;
-    size_t stage, scratch, stage_sz, scratch_sz, stage_off, scratch_off, total;
-};
-static inline ZstdCompactTemp zstd_compact_temp(int level, size_t total_in, size_t max_bytes, size_t nchunks) {
-    ZstdCompactTemp t;
+static inline CompactTemp zstd_compact_temp(int level, size_t total_in, size_t max_bytes, size_t nchunks) {
+    CompactTemp t = {};   // (no record counts: hdr stays 0)
     TempCursor c;
     t.reg = lzh_zstd_compact_regions(level, total_in, max_bytes, nchunks);
     t.stage = c.take(t.reg.stage, kGap);
-    t.scratch = c.take(t.reg.scratch, kGap);
-    t.stage_sz = c.take(nchunks * 4);
-    t.scratch_sz = c.take(nchunks * 4);
-    t.stage_off = c.take((nchunks + 1) * 8);
-    t.scratch_off = c.take((nchunks + 1) * 8);
-    t.total = c.at;
+    t.recs = c.take(t.reg.recs, kGap);
+    compact_arrays(t, c, nchunks, 0);
     return t;
 }
 

@@ -11,12 +11,12 @@
 //                                   carrying the scratch slots
 //
 // A chunk is processed exactly when its size is at most max_bytes and both of its slots end inside their
-// regions (zcompact_span below; the host sizes the regions for the promised total, api.cpp).  Any other chunk is
+// regions (compact_span, ragged_slots.h; the host sizes the regions for the promised total, api.cpp).  Any other chunk is
 // handled as an oversize chunk of zstd_ragged_hip.hip: csizes[i] = 0, no packed bytes, no kernel touches a slot.
 //
 // The kernel bodies are the uniform kernels' text (zstdc_match_body.inc, zstdc_entropy_body.inc), unchanged.  They
 // name a frame's scratch `scratch + f * fstride`, its staging slot `stage + f * stride` of `stride` bytes, and
-// the areas inside the scratch by seq_off .. tab_off.  Here fstride and stride are ZSlot values -- f * slot is the
+// the areas inside the scratch by seq_off .. tab_off.  Here fstride and stride are ZstdSlot values (a CompactSlot of ragged_slots.h) -- f * slot is the
 // slot's scanned offset, the slot converted to an integer its own size -- and the five offsets are locals laid
 // out for the chunk's own parameters (lzh_zslot_layout: the layout whose stride is the slot's size), where the
 // uniform-slot kernels get them as arguments computed for max_bytes.  Every buffer descriptor the bodies build is
@@ -27,26 +27,11 @@
 #include "zstdc_hip.hip"
 #include "zstd_ragged_slots.h"
 
-struct ZSlot {
-    uint64_t off;     // from the region's base (a multiple of 256)
-    uint32_t bytes;
-    // (the bodies pass a slot where they mean its size: `out.init(stage + f * stride, stride)`)
+// (the bodies pass a slot where they mean its size, `out.init(stage + f * stride, stride)`: the conversion that the
+// LZ4 / snappy bodies must spell as a cast is implicit here)
+struct ZstdSlot : CompactSlot {
     __device__ __forceinline__ operator uint64_t() const { return bytes; }
 };
-__device__ __forceinline__ uint64_t operator*(uint64_t, ZSlot s) { return s.off; }
-
-// Chunk i of a compact batch: ragged_span's pointer and size and the chunk's two slots, loaded once and
-// wave-uniform.  false = not processed (over max_bytes, or a slot that ends past its region).
-__device__ __forceinline__ bool zcompact_span(const void* const* ptrs, const uint64_t* bytes, uint64_t i,
-                                              uint64_t max_bytes, const LzhCompactLayout& C, const uint8_t*& p, int& n,
-                                              ZSlot& stage_slot, ZSlot& scratch_slot) {
-    if (!ragged_span(ptrs, bytes, i, max_bytes, p, n)) return false;
-    stage_slot.off = uni64(C.stage_off[i]);
-    stage_slot.bytes = uni(C.stage_sz[i]);
-    scratch_slot.off = uni64(C.rec_off[i]);
-    scratch_slot.bytes = uni(C.rec_sz[i]);
-    return stage_slot.off + stage_slot.bytes <= C.stage_cap && scratch_slot.off + scratch_slot.bytes <= C.rec_cap;
-}
 
 // -------------------------------------------------------------------------------------- slot sizes
 extern "C" __global__ void __launch_bounds__(256)
@@ -72,8 +57,8 @@ lzh_zstd_match_compact_kernel(const void* const* in_ptrs, const uint64_t* in_byt
     const uint64_t ioff = 0;
     const uint8_t* in;
     int sn;
-    ZSlot stride, fstride;
-    if (!zcompact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) return;
+    ZstdSlot stride, fstride;
+    if (!compact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) return;
     const uint64_t nf = (uint64_t)sn;
     const uint64_t in_readable = nf + 16;
     const Layout Lo = lzh_zslot_layout(lzh_zslot_params(level, nf));
@@ -91,8 +76,8 @@ lzh_zstd_entropy_compact_kernel(const void* const* in_ptrs, const uint64_t* in_b
     const uint64_t ioff = 0;
     const uint8_t* in;
     int sn;
-    ZSlot stride, fstride;
-    if (!zcompact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) {
+    ZstdSlot stride, fstride;
+    if (!compact_span(in_ptrs, in_bytes, f, max_bytes, C, in, sn, stride, fstride)) {
         if (lane == 0 && k == 0) csizes[f] = 0;
         return;
     }
@@ -106,13 +91,12 @@ lzh_zstd_entropy_compact_kernel(const void* const* in_ptrs, const uint64_t* in_b
 // ------------------------------------------------------------------------- host side: arithmetic, launcher
 #include <algorithm>
 
-LzhZstdCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
+LzhCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
     return lzh_zslot_regions(level, total, max_bytes, nchunks);
 }
 
-void lzh_zstd_compact_slot(int level, uint64_t n, uint64_t* stage_bytes, uint64_t* scratch_bytes) {
-    *stage_bytes = lzh_zslot_stage_bytes(n);
-    *scratch_bytes = lzh_zslot_scratch_bytes(level, n);
+LzhCompactRegions lzh_zstd_compact_slot(int level, uint64_t n) {
+    return {lzh_zslot_stage_bytes(n), lzh_zslot_scratch_bytes(level, n)};
 }
 
 hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
@@ -127,10 +111,7 @@ hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* i
     hipLaunchKernelGGL(lzh_zstd_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes, max_bytes,
                        level, L.stage_sz, L.rec_sz, nchunks);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = lzh_launch_scan(L.stage_sz, nchunks, L.stage_off, nullptr, s);
-    if (e != hipSuccess) return e;
-    e = lzh_launch_scan(L.rec_sz, nchunks, L.rec_off, nullptr, s);
+    if (e == hipSuccess) e = lzh_launch_compact_scans(L, nchunks, s);
     if (e != hipSuccess) return e;
     const uint32_t nblocks = (uint32_t)((geo + PF.bsize - 1) / PF.bsize);
     const uint32_t lds_tab = lzh_zstd_lds_table(level, geo);

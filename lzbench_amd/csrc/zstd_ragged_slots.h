@@ -74,14 +74,14 @@ LZH_HD uint64_t lzh_zslot_scratch_worst(int level, uint64_t max_bytes) {
 // Every term is non-decreasing in each argument, so both answers are.
 // Range: as lzh_compact_regions, u64 arithmetic without overflow checks (16 x total needs total < 2^60).
 LZH_HD uint64_t lzh_zslot_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
-LZH_HD LzhZstdCompactRegions lzh_zslot_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
+LZH_HD LzhCompactRegions lzh_zslot_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
     const uint64_t bmax = lzh_zslot_min(max_bytes ? max_bytes : 1, 131072);
     const uint64_t tmax = 4ull << lzh_zslot_hlog_worst(level, max_bytes);
     const uint64_t st = total + (total >> 8) + nchunks * 335;
     const uint64_t sc = lzh_zslot_min(8 * total, nchunks * 8 * bmax) + nchunks * 6656 +
                         lzh_zslot_min(16 * total + nchunks * 512, nchunks * tmax);
-    LzhZstdCompactRegions r;
+    LzhCompactRegions r;   // (recs: the scratch region)
     r.stage = lzh_slot_align(lzh_zslot_min(st, nchunks * lzh_zslot_stage_bytes(max_bytes)));
-    r.scratch = lzh_slot_align(lzh_zslot_min(sc, nchunks * lzh_zslot_scratch_worst(level, max_bytes)));
+    r.recs = lzh_slot_align(lzh_zslot_min(sc, nchunks * lzh_zslot_scratch_worst(level, max_bytes)));
     return r;
 }

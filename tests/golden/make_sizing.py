@@ -6,12 +6,14 @@ sizing.json pins what the sizing calls returned before that was so, for tests/te
 arithmetic: needs the built liblzbench_hip.so, no GPU and no reference build.  Run on the commit whose answers are
 to be pinned (python tests/golden/make_sizing.py); LZH_LIB names another build of the library.
 
-Writes sizing.json and, for the ragged zstd calls, sizing_zstd_ragged.json, each {"grid": {...}, "tables":
+Writes sizing.json, for the ragged zstd calls sizing_zstd_ragged.json and for their compact layout
+sizing_zstd_ragged_compact.json, each {"grid": {...}, "tables":
 {function: {codec number: [values in the grid's loop order]}}, "sha256": digest of the tables}.  Loop order: the arguments in the order of the C declaration, the first one
 outermost.  lzh_debug_ragged_compact_regions gives four values per point; lzh_debug_plan gives, per point, its
 return value and then that many values.  The ragged zstd calls (levels 1 and -1 where they take one, over
 chunk x nchunks) have one list each, under codec "3"; lzh_debug_zstd_ragged_split_layout gives its 16 values per
-point, or its error code 16 times.
+point, or its error code 16 times.  The two compact ones (levels 1 and -1 over n x chunk x nchunks, n the batch's
+total bytes): lzh_debug_zstd_ragged_compact_regions gives four values per point, or its error code four times.
 """
 from __future__ import annotations
 
@@ -88,6 +90,20 @@ def tables(lib) -> dict:
                  "lzh_zstd_ragged_max_packed_bytes"):   # (the last one's first argument is the batch's total bytes)
         zstd_table(name, (getattr(lib, name)(m, k) for m in CH for k in K))
     zstd_table("lzh_debug_zstd_ragged_split_layout", split_layout())
+
+    def zstd_regions():
+        r = (C.c_uint64 * 4)()
+        for lv in (1, -1):
+            for t in N:
+                for m in CH:
+                    for k in K:
+                        rc = lib.lzh_debug_zstd_ragged_compact_regions(lv, t, m, k, r)
+                        yield from (list(r) if rc == 0 else [rc] * 4)
+
+    zstd_table("lzh_zstd_ragged_compact_compress_temp_bytes",
+               (lib.lzh_zstd_ragged_compact_compress_temp_bytes(lv, t, m, k)
+                for lv in (1, -1) for t in N for m in CH for k in K))
+    zstd_table("lzh_debug_zstd_ragged_compact_regions", zstd_regions())
     return out
 
 
@@ -96,10 +112,12 @@ def digest(tabs: dict) -> str:
 
 
 def files(tabs: dict) -> dict:
-    """{file name: its tables}: the ragged zstd tables have a file of their own, so that adding them left
-    sizing.json, a single line of 190 KB, as it was."""
-    own = {name: t for name, t in tabs.items() if "zstd_ragged" in name}
-    return {"sizing.json": {name: t for name, t in tabs.items() if name not in own}, "sizing_zstd_ragged.json": own}
+    """{file name: its tables}: the ragged zstd tables have a file of their own, and those of their compact layout
+    another, so that adding them left sizing.json, a single line of 190 KB, and then both files as they were."""
+    compact = {name: t for name, t in tabs.items() if "zstd_ragged_compact" in name}
+    own = {name: t for name, t in tabs.items() if "zstd_ragged" in name and name not in compact}
+    return {"sizing.json": {name: t for name, t in tabs.items() if "zstd_ragged" not in name},
+            "sizing_zstd_ragged.json": own, "sizing_zstd_ragged_compact.json": compact}
 
 
 def main():

@@ -1,6 +1,7 @@
 """CPU: every sizing entry point of the device API answers what tests/golden/sizing*.json recorded (the temp layouts
-of lzbench_amd/csrc/temp_layout.h give the sizes the hand-kept sums gave before them), and the ragged uniform-slot
-compress temp is the uniform call's for the same slots."""
+of lzbench_amd/csrc/temp_layout.h give the sizes the hand-kept sums gave before them; sizing_zstd_ragged_compact.json
+holds the compact zstd layout's sizes and regions from before it shared the LZ4 / snappy layout's struct), and the
+ragged uniform-slot compress temp is the uniform call's for the same slots."""
 import importlib.util
 import json
 import os
@@ -19,7 +20,7 @@ def _maker():
 
 def test_sizing_answers_equal_the_recorded_ones():
     M = _maker()
-    for fname, got in M.files(M.tables(L.lib())).items():   # (sizing.json, and the ragged zstd calls' file)
+    for fname, got in M.files(M.tables(L.lib())).items():   # (sizing.json, the ragged zstd calls' file, their compact layout's)
         with open(os.path.join(GOLDEN, fname)) as f:
             want = json.load(f)
         assert want["grid"] == M.GRID, f"{fname} was made over another grid"
