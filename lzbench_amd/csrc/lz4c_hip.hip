@@ -41,6 +41,17 @@ constexpr int kRing = 1024;           // bytes of LDS input ring per wave
 constexpr int kAhead = 704;           // keep the ring filled this far past the batch front
 constexpr int kOut = 512;             // bytes of LDS output ring per wave
 
+// Step counters of the slow count (256 bytes a step) and the slow catch-up (64 bytes a step).  Both loops end by
+// themselves, at matchlimit and at the anchor / the block start: LZ4_count and the catch-up of lz4.c have no other
+// limit, and a limit a match can reach cuts it (1024 and 4096 steps did: tests/test_gpu_lzc_census.py).  The
+// counters stay because the batch loop compiles slower without them: on 1 GiB of text, three alternating benchmark
+// runs each, 62.04 .. 62.05 GB/s without against 62.49 .. 62.75 with (the parse kernel 12.30 .. 12.31 ms against
+// 12.14 .. 12.17: the gap is eight times either build's own spread); with them the kernel times as before
+// (12.15 .. 12.20 ms).  A compiler that no longer shows the gap makes them removable.  Their bounds are out of any
+// chunk's reach: a chunk is under 2^31 bytes, these are 2^33.
+constexpr int kCountSteps = 1 << 25;
+constexpr int kCatchupSteps = 1 << 27;
+
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 __device__ __forceinline__ int64_t step_prefix(int64_t M) {
@@ -463,7 +474,7 @@ __device__ __forceinline__ int finish_match(const Bytes& in, int P, int M, int b
     if (bkr == 4 && maxb > 4) {
         LZ_STAT(5, 1);
         int ip2 = P - 4, m2 = M - 4;
-        for (int it = 0; it < (1 << 12); it++) {
+        for (int it = 0; it < kCatchupSteps; it++) {
             const int mb2 = min(ip2 - anchor, m2);
             if (mb2 <= 0) break;
             const bool e2b = lane < mb2 && in.b(ip2 - 1 - lane) == in.b(m2 - 1 - lane);
@@ -478,7 +489,7 @@ __device__ __forceinline__ int finish_match(const Bytes& in, int P, int M, int b
     int cnt = len;
     if (len == 20 && a + cnt < mlimit) {
         LZ_STAT(6, 1);
-        for (int it = 0; it < (1 << 10) && a + cnt < mlimit; it++) {
+        for (int it = 0; it < kCountSteps && a + cnt < mlimit; it++) {
             const int o = cnt + 4 * lane;
             const uint32_t x = in.w32(a + o) ^ in.w32(M + kMinMatch + o);
             const uint64_t ne = ballot(x != 0);
@@ -498,7 +509,7 @@ __device__ __forceinline__ int finish_match(const Bytes& in, int P, int M, int b
 // bounded by the anchor and the block start; lane-parallel compare, 64 bytes per step
 __device__ __forceinline__ int slow_catchup(const Bytes& in, int P, int M, int anchor, int lane) {
     int ip2 = P - 4, m2 = M - 4;
-    for (int it = 0; it < (1 << 12); it++) {
+    for (int it = 0; it < kCatchupSteps; it++) {
         const int mb2 = min(ip2 - anchor, m2);
         if (mb2 <= 0) break;
         const bool e2b = lane < mb2 && in.b(ip2 - 1 - lane) == in.b(m2 - 1 - lane);
@@ -515,7 +526,7 @@ __device__ __forceinline__ int slow_catchup(const Bytes& in, int P, int M, int a
 __device__ __forceinline__ int slow_count(const Bytes& in, int P, int M, int mlimit, int lane) {
     const int a = P + kMinMatch;
     int cnt = 20;
-    for (int it = 0; it < (1 << 10) && a + cnt < mlimit; it++) {
+    for (int it = 0; it < kCountSteps && a + cnt < mlimit; it++) {
         const int o = cnt + 4 * lane;
         const uint32_t x = in.w32(a + o) ^ in.w32(M + kMinMatch + o);
         const uint64_t ne = ballot(x != 0);

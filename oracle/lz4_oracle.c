@@ -53,8 +53,18 @@ static int lz4o_put_len(uint8_t* dst, int op, int len) {
     return op;
 }
 
-int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleration) {
+/* encoder events (oracle.h ORACLE_LZ4C_*; tests/lzc_census.py names them); c == NULL: nothing is counted */
+#define CNT(i) do { if (c) c[ORACLE_LZ4C_##i]++; } while (0)
+
+static void lz4o_count_lit(uint64_t* c, int lit) {
+    if (lit == 0) CNT(LIT_0); else if (lit < 15) CNT(LIT_1_14); else if (lit == 15) CNT(LIT_15);
+    else if (lit < 256) CNT(LIT_16_255); else CNT(LIT_256UP);
+    if (lit == 270) CNT(LIT_270);
+}
+
+static int lz4o_compress(const uint8_t* src, int n, uint8_t* dst, int acceleration, uint64_t* c) {
     static __thread lz4o_tab tab;           /* 48 KiB, keep it off the stack */
+    int chain = 0;                          /* consecutive re-test hits */
     if (acceleration < 1) acceleration = 1;
     if (acceleration > 65537) acceleration = 65537;
     if (n <= 0) { dst[0] = 0; return 1; }
@@ -69,7 +79,8 @@ int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleratio
     int ip = 0, anchor = 0, op = 0;
     uint32_t fh;
 
-    if (n < LZ4O_MINLENGTH) goto last_literals;
+    if (t->small) CNT(TAB_U16); else CNT(TAB_U32);
+    if (n < LZ4O_MINLENGTH) { CNT(N_LT_13); goto last_literals; }
 
     lz4o_put(t, lz4o_hash(t, 0), 0);
     ip = 1;
@@ -87,18 +98,33 @@ int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleratio
                 ip = fwd;
                 fwd += step;
                 step = nb++ >> 6;
-                if (fwd > mfl1) goto last_literals;
+                if (fwd > mfl1) { CNT(END_SEARCH); goto last_literals; }
+                if (fwd - cur > acceleration) { if (acceleration == 1) CNT(STEP_GT_1); else CNT(STEP_GT_ACC); }
                 fh = lz4o_hash(t, fwd);
                 lz4o_put(t, h, (uint32_t)cur);
-                if (!t->small && cand + 65535u < (uint32_t)cur) continue;   /* too far */
+                if (!t->small && cand + 65535u < (uint32_t)cur) {   /* too far */
+                    CNT(FAR_REJECTED);
+                    if ((uint32_t)cur - cand == 65536u) CNT(FAR_65536);
+                    continue;
+                }
                 if (rd32(src + cand) == rd32(src + ip)) { match = (int)cand; break; }
             }
         }
         /* extend backwards over equal bytes */
-        while (ip > anchor && match > 0 && src[ip - 1] == src[match - 1]) { ip--; match--; }
+        {
+            int bk = 0;
+            while (ip > anchor && match > 0 && src[ip - 1] == src[match - 1]) { ip--; match--; bk++; }
+            CNT(HIT_SEARCH);
+            chain = 0;
+            if (bk == 0) CNT(CATCHUP_0); else if (bk < 4) CNT(CATCHUP_1_3); else if (bk == 4) CNT(CATCHUP_4);
+            else if (bk <= 64) CNT(CATCHUP_5_64); else CNT(CATCHUP_GT_64);
+            if (bk && ip == anchor) CNT(CATCHUP_TO_ANCHOR);
+            if (bk && match == 0) CNT(CATCHUP_TO_START);
+        }
 
         {   /* token + literal run */
             int lit = ip - anchor;
+            lz4o_count_lit(c, lit);
             tok = op++;
             if (lit >= 15) { dst[tok] = 15 << 4; op = lz4o_put_len(dst, op, lit - 15); }
             else dst[tok] = (uint8_t)(lit << 4);
@@ -112,19 +138,33 @@ int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleratio
             dst[op++] = (uint8_t)(off & 0xff);
             dst[op++] = (uint8_t)(off >> 8);
             int ml = lz4o_common(src, ip + LZ4O_MINMATCH, match + LZ4O_MINMATCH, mlimit);
+            CNT(SEQUENCES);
+            if (off == 1) CNT(OFF_1); else if (off <= 3) CNT(OFF_2_3); else if (off == 65535) CNT(OFF_65535);
+            if (ml == 0) CNT(COUNT_0); else if (ml < 20) CNT(COUNT_1_19); else if (ml == 20) CNT(COUNT_20);
+            else if (ml <= 275) CNT(COUNT_21_275); else CNT(COUNT_GT_275);
+            if (ml > 262164) CNT(COUNT_GT_262164);
+            if (ip + LZ4O_MINMATCH + ml == mlimit) CNT(COUNT_TO_MATCHLIMIT);
+            if (ml == 15) CNT(ML_15);
+            if (ml == 15 + 255) CNT(ML_15_255);
             ip += ml + LZ4O_MINMATCH;
             if (ml >= 15) { dst[tok] = (uint8_t)(dst[tok] + 15); op = lz4o_put_len(dst, op, ml - 15); }
             else dst[tok] = (uint8_t)(dst[tok] + ml);
         }
         anchor = ip;
-        if (ip >= mfl1) break;
+        if (ip >= mfl1) { CNT(END_MATCH); break; }
 
         lz4o_put(t, lz4o_hash(t, ip - 2), (uint32_t)(ip - 2));
         {   /* immediate re-test at the match end (no catch-up on this path) */
             uint32_t h = lz4o_hash(t, ip);
             uint32_t cand = lz4o_get(t, h);
             lz4o_put(t, h, (uint32_t)ip);
-            if ((t->small || cand + 65535u >= (uint32_t)ip) && rd32(src + cand) == rd32(src + ip)) {
+            if (!t->small && cand + 65535u < (uint32_t)ip) {
+                CNT(FAR_REJECTED);
+                if ((uint32_t)ip - cand == 65536u) CNT(FAR_65536);
+            } else if (rd32(src + cand) == rd32(src + ip)) {
+                CNT(HIT_RETEST);
+                if (++chain == 8) CNT(RETEST_CHAIN_8);
+                lz4o_count_lit(c, 0);
                 match = (int)cand;
                 tok = op++;
                 dst[tok] = 0;
@@ -138,12 +178,22 @@ int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleratio
 last_literals:
     {
         int run = n - anchor;
+        if (run == LZ4O_LASTLITERALS) CNT(LAST_LITERALS_5);
         if (run >= 15) { dst[op++] = 15 << 4; op = lz4o_put_len(dst, op, run - 15); }
         else dst[op++] = (uint8_t)(run << 4);
         memcpy(dst + op, src + anchor, (size_t)run);
         op += run;
     }
     return op;
+}
+#undef CNT
+
+int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleration) {
+    return lz4o_compress(src, n, dst, acceleration, NULL);
+}
+
+int oracle_lz4_compress_census(const uint8_t* src, int n, uint8_t* dst, int acceleration, uint64_t* c) {
+    return lz4o_compress(src, n, dst, acceleration, c);
 }
 
 /* ---------------------------------------------------------------- decoder */

@@ -23,6 +23,23 @@ extern "C" {
 /* LZ4 block compression, LZ4_compress_fast(src,dst,n,cap>=bound,acc) semantics
  * (reference lz4/lz4.c:1284-1305 notLimited path, :851-1240 parser). Returns bytes written. */
 int oracle_lz4_compress(const uint8_t* src, int n, uint8_t* dst, int acceleration);
+/* The same compressor, counting its parser's events into c[ORACLE_LZ4C_N] (added to what c holds; the bytes
+ * written are oracle_lz4_compress's: one body).  tests/lzc_census.py names and documents the events. */
+enum {
+    ORACLE_LZ4C_TAB_U16, ORACLE_LZ4C_TAB_U32, ORACLE_LZ4C_N_LT_13,
+    ORACLE_LZ4C_HIT_SEARCH, ORACLE_LZ4C_HIT_RETEST, ORACLE_LZ4C_RETEST_CHAIN_8,
+    ORACLE_LZ4C_CATCHUP_0, ORACLE_LZ4C_CATCHUP_1_3, ORACLE_LZ4C_CATCHUP_4, ORACLE_LZ4C_CATCHUP_5_64,
+    ORACLE_LZ4C_CATCHUP_GT_64, ORACLE_LZ4C_CATCHUP_TO_ANCHOR, ORACLE_LZ4C_CATCHUP_TO_START,
+    ORACLE_LZ4C_COUNT_0, ORACLE_LZ4C_COUNT_1_19, ORACLE_LZ4C_COUNT_20, ORACLE_LZ4C_COUNT_21_275,
+    ORACLE_LZ4C_COUNT_GT_275, ORACLE_LZ4C_COUNT_GT_262164, ORACLE_LZ4C_COUNT_TO_MATCHLIMIT,
+    ORACLE_LZ4C_LIT_0, ORACLE_LZ4C_LIT_1_14, ORACLE_LZ4C_LIT_15, ORACLE_LZ4C_LIT_16_255, ORACLE_LZ4C_LIT_256UP,
+    ORACLE_LZ4C_LIT_270, ORACLE_LZ4C_ML_15, ORACLE_LZ4C_ML_15_255,
+    ORACLE_LZ4C_OFF_1, ORACLE_LZ4C_OFF_2_3, ORACLE_LZ4C_OFF_65535, ORACLE_LZ4C_FAR_REJECTED, ORACLE_LZ4C_FAR_65536,
+    ORACLE_LZ4C_STEP_GT_1, ORACLE_LZ4C_STEP_GT_ACC,
+    ORACLE_LZ4C_END_SEARCH, ORACLE_LZ4C_END_MATCH, ORACLE_LZ4C_LAST_LITERALS_5, ORACLE_LZ4C_SEQUENCES,
+    ORACLE_LZ4C_N
+};
+int oracle_lz4_compress_census(const uint8_t* src, int n, uint8_t* dst, int acceleration, uint64_t* c);
 /* LZ4_compressBound (reference lz4/lz4.h:171). */
 int oracle_lz4_bound(int n);
 /* LZ4_decompress_safe semantics (reference lz4/lz4.c:1737-2165 safe loop, :2170-2176).
@@ -32,6 +49,21 @@ int oracle_lz4_decompress_prefix(const uint8_t* src, int csize, uint8_t* dst, in
 
 /* snappy::RawCompress (reference snappy/snappy.cc:1043-1111, :510-681). Returns bytes written. */
 size_t oracle_snappy_compress(const uint8_t* src, size_t n, uint8_t* dst);
+/* The same compressor, counting its parser's events into c[ORACLE_SNC_N] (added to what c holds; one body).
+ * TABLE_256 + k: a fragment with a table of 256 << k entries (k = 0..6).  tests/lzc_census.py names the events. */
+enum {
+    ORACLE_SNC_TABLE_256, ORACLE_SNC_TABLE_512, ORACLE_SNC_TABLE_1024, ORACLE_SNC_TABLE_2048, ORACLE_SNC_TABLE_4096,
+    ORACLE_SNC_TABLE_8192, ORACLE_SNC_TABLE_16384,
+    ORACLE_SNC_FRAG_LT_15, ORACLE_SNC_FRAGS_1, ORACLE_SNC_FRAGS_2, ORACLE_SNC_FRAGS_4UP,
+    ORACLE_SNC_HIT_SEARCH, ORACLE_SNC_HIT_RETEST, ORACLE_SNC_PROBE_PAST_16, ORACLE_SNC_PROBE_OFF_GT_63,
+    ORACLE_SNC_SEARCH_RAN_OUT, ORACLE_SNC_END_COPY,
+    ORACLE_SNC_COPY1, ORACLE_SNC_COPY2_LEN, ORACLE_SNC_COPY2_OFF,
+    ORACLE_SNC_COPY_64, ORACLE_SNC_COPY_65_67, ORACLE_SNC_COPY_68, ORACLE_SNC_COPY_132UP,
+    ORACLE_SNC_LIT_1_60, ORACLE_SNC_LIT_61_256, ORACLE_SNC_LIT_257_65536, ORACLE_SNC_LIT_GT_256_BEFORE_COPY,
+    ORACLE_SNC_LIT_REMAINDER,
+    ORACLE_SNC_N
+};
+size_t oracle_snappy_compress_census(const uint8_t* src, size_t n, uint8_t* dst, uint64_t* c);
 /* snappy::MaxCompressedLength (reference snappy/snappy.cc:99-121). */
 size_t oracle_snappy_bound(size_t n);
 /* snappy::RawUncompress (reference snappy/snappy.cc:848-1036, :1398-1407).

@@ -26,8 +26,12 @@ static uint32_t table_size_for(uint32_t n) {
     return 2u << log2floor(n - 1);
 }
 
-static size_t emit_literal(uint8_t* dst, size_t op, const uint8_t* lit, int len) {
+/* encoder events (oracle.h ORACLE_SNC_*; tests/lzc_census.py names them); c == NULL: nothing is counted */
+#define CNT(i) do { if (c) c[ORACLE_SNC_##i]++; } while (0)
+
+static size_t emit_literal(uint8_t* dst, size_t op, const uint8_t* lit, int len, uint64_t* c) {
     int n = len - 1;
+    if (len <= 60) CNT(LIT_1_60); else if (len <= 256) CNT(LIT_61_256); else CNT(LIT_257_65536);
     if (n < 60) {
         dst[op++] = (uint8_t)(n << 2);
     } else {
@@ -39,7 +43,8 @@ static size_t emit_literal(uint8_t* dst, size_t op, const uint8_t* lit, int len)
     return op + (size_t)len;
 }
 
-static size_t emit_copy_le64(uint8_t* dst, size_t op, uint32_t off, int len) {
+static size_t emit_copy_le64(uint8_t* dst, size_t op, uint32_t off, int len, uint64_t* c) {
+    if (len < 12 && off < 2048) CNT(COPY1); else if (len >= 12) CNT(COPY2_LEN); else CNT(COPY2_OFF);
     if (len < 12 && off < 2048) {          /* COPY_1: 3-bit len-4, 11-bit offset */
         dst[op++] = (uint8_t)(1 | ((len - 4) << 2) | ((off >> 8) << 5));
         dst[op++] = (uint8_t)(off & 0xff);
@@ -51,18 +56,23 @@ static size_t emit_copy_le64(uint8_t* dst, size_t op, uint32_t off, int len) {
     return op;
 }
 
-static size_t emit_copy(uint8_t* dst, size_t op, uint32_t off, int len) {
-    if (len < 12) return emit_copy_le64(dst, op, off, len);
-    while (len >= 68) { op = emit_copy_le64(dst, op, off, 64); len -= 64; }
-    if (len > 64) { op = emit_copy_le64(dst, op, off, 60); len -= 60; }
-    return emit_copy_le64(dst, op, off, len);
+static size_t emit_copy(uint8_t* dst, size_t op, uint32_t off, int len, uint64_t* c) {
+    if (len == 64) CNT(COPY_64); else if (len >= 65 && len <= 67) CNT(COPY_65_67); else if (len == 68) CNT(COPY_68);
+    if (len >= 132) CNT(COPY_132UP);
+    if (len < 12) return emit_copy_le64(dst, op, off, len, c);
+    while (len >= 68) { op = emit_copy_le64(dst, op, off, 64, c); len -= 64; }
+    if (len > 64) { op = emit_copy_le64(dst, op, off, 60, c); len -= 60; }
+    return emit_copy_le64(dst, op, off, len, c);
 }
 
 /* one fragment (<= 64 KiB); offsets are relative to the fragment start */
-static size_t compress_fragment(const uint8_t* in, uint32_t n, uint8_t* dst, size_t op, uint16_t* table) {
+static size_t compress_fragment(const uint8_t* in, uint32_t n, uint8_t* dst, size_t op, uint16_t* table,
+                                uint64_t* c) {
     const uint32_t tsize = table_size_for(n);
     const int shift = 32 - log2floor(tsize);
     memset(table, 0, tsize * sizeof(uint16_t));
+    if (c) c[ORACLE_SNC_TABLE_256 + log2floor(tsize) - 8]++;
+    if (n < 15) CNT(FRAG_LT_15);
 
     uint32_t ip = 0, next_emit = 0;
     if (n >= 15) {
@@ -93,22 +103,26 @@ static size_t compress_fragment(const uint8_t* in, uint32_t n, uint8_t* dst, siz
                     uint32_t step = skip >> 5;
                     skip += step;
                     uint32_t next_ip = ip + step;
-                    if (next_ip > ip_limit) { ip = next_emit; goto remainder; }
+                    if (next_ip > ip_limit) { CNT(SEARCH_RAN_OUT); ip = next_emit; goto remainder; }
+                    CNT(PROBE_PAST_16);       /* (a probe of the loop after the unrolled ones) */
+                    if (ip - (next_emit + 1) > 63) CNT(PROBE_OFF_GT_63);
                     cand = table[h];
                     table[h] = (uint16_t)ip;
                     if (v == rd32(in + cand)) break;
                     ip = next_ip;
                 }
             }
-            op = emit_literal(dst, op, in + next_emit, (int)(ip - next_emit));
+            CNT(HIT_SEARCH);
+            if (ip - next_emit > 256) CNT(LIT_GT_256_BEFORE_COPY);
+            op = emit_literal(dst, op, in + next_emit, (int)(ip - next_emit), c);
             /* copy loop: keep emitting while the position right after a copy matches */
             for (;;) {
                 uint32_t base = ip;
                 uint32_t m = 4;
                 while (ip + m < n && in[cand + m] == in[ip + m]) m++;
                 ip += m;
-                op = emit_copy(dst, op, base - cand, (int)m);
-                if (ip >= ip_limit) goto remainder;
+                op = emit_copy(dst, op, base - cand, (int)m, c);
+                if (ip >= ip_limit) { CNT(END_COPY); goto remainder; }
                 uint32_t hm1 = (rd32(in + ip - 1) * 0x1e35a7bdu) >> shift;
                 table[hm1] = (uint16_t)(ip - 1);
                 uint32_t v = rd32(in + ip);
@@ -116,25 +130,35 @@ static size_t compress_fragment(const uint8_t* in, uint32_t n, uint8_t* dst, siz
                 cand = table[h];
                 table[h] = (uint16_t)ip;
                 if (v != rd32(in + cand)) break;
+                CNT(HIT_RETEST);
             }
         }
     }
 remainder:
-    if (ip < n) op = emit_literal(dst, op, in + ip, (int)(n - ip));
+    if (ip < n) { CNT(LIT_REMAINDER); op = emit_literal(dst, op, in + ip, (int)(n - ip), c); }
     return op;
 }
 
-size_t oracle_snappy_compress(const uint8_t* src, size_t n, uint8_t* dst) {
+static size_t snappy_compress(const uint8_t* src, size_t n, uint8_t* dst, uint64_t* c) {
     static __thread uint16_t table[1 << 14];
     size_t op = 0;
+    const size_t frags = (n + 65535) / 65536;
+    if (frags == 1) CNT(FRAGS_1); else if (frags == 2) CNT(FRAGS_2); else if (frags >= 4) CNT(FRAGS_4UP);
     uint32_t v = (uint32_t)n;
     while (v >= 128) { dst[op++] = (uint8_t)(v | 128); v >>= 7; }   /* varint32 length */
     dst[op++] = (uint8_t)v;
     for (size_t pos = 0; pos < n; pos += 65536) {
         uint32_t frag = (uint32_t)((n - pos) < 65536 ? (n - pos) : 65536);
-        op = compress_fragment(src + pos, frag, dst, op, table);
+        op = compress_fragment(src + pos, frag, dst, op, table, c);
     }
     return op;
+}
+#undef CNT
+
+size_t oracle_snappy_compress(const uint8_t* src, size_t n, uint8_t* dst) { return snappy_compress(src, n, dst, NULL); }
+
+size_t oracle_snappy_compress_census(const uint8_t* src, size_t n, uint8_t* dst, uint64_t* c) {
+    return snappy_compress(src, n, dst, c);
 }
 
 int64_t oracle_snappy_uncompress(const uint8_t* src, size_t csize, uint8_t* dst, size_t cap) {

@@ -25,6 +25,10 @@ def oracle():
         L = C.CDLL(ORACLE_PATH)
         L.oracle_lz4_compress.restype = C.c_int
         L.oracle_lz4_compress.argtypes = [_P, C.c_int, _P, C.c_int]
+        L.oracle_lz4_compress_census.restype = C.c_int
+        L.oracle_lz4_compress_census.argtypes = [_P, C.c_int, _P, C.c_int, _P]
+        L.oracle_snappy_compress_census.restype = _SZ
+        L.oracle_snappy_compress_census.argtypes = [_P, _SZ, _P, _P]
         L.oracle_lz4_bound.restype = C.c_int
         L.oracle_lz4_bound.argtypes = [C.c_int]
         L.oracle_lz4_decompress_safe.restype = C.c_int
@@ -125,6 +129,27 @@ def snappy_compress(data: np.ndarray) -> bytes:
     out = np.zeros(L.oracle_snappy_bound(len(data)) + 64, np.uint8)
     r = L.oracle_snappy_compress(data.ctypes.data, len(data), out.ctypes.data)
     return out[:r].tobytes()
+
+
+def lz4_compress_census(data: np.ndarray, acc: int = 1):
+    """(bytes, counters) of oracle_lz4_compress_census: the compressed chunk and the parser's event counts, in the
+    order of oracle.h's ORACLE_LZ4C_* (tests/lzc_census.py names them)"""
+    L = oracle()
+    data = np.ascontiguousarray(data)
+    out = np.zeros(L.oracle_lz4_bound(len(data)) + 64, np.uint8)
+    c = np.zeros(64, np.uint64)
+    r = L.oracle_lz4_compress_census(data.ctypes.data, len(data), out.ctypes.data, acc, c.ctypes.data)
+    return out[:r].tobytes(), c
+
+
+def snappy_compress_census(data: np.ndarray):
+    """(bytes, counters) of oracle_snappy_compress_census, in the order of oracle.h's ORACLE_SNC_*"""
+    L = oracle()
+    data = np.ascontiguousarray(data)
+    out = np.zeros(L.oracle_snappy_bound(len(data)) + 64, np.uint8)
+    c = np.zeros(64, np.uint64)
+    r = L.oracle_snappy_compress_census(data.ctypes.data, len(data), out.ctypes.data, c.ctypes.data)
+    return out[:r].tobytes(), c
 
 
 def compress_chunks(data: np.ndarray, codec: str, chunk: int, level: int = 1, use_ref=None, threads: int = 0):
