@@ -348,6 +348,41 @@ int lzh_debug_zstd_ragged_compact_slots(int level, const uint64_t* sizes, size_t
 int lzh_debug_zstd_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                           uint64_t* out);
 
+/* Debug only, host arithmetic only (they may change; no decode call takes this layout yet, so the split decoder runs
+ * with the uniform-slot temp above alone and there is no public sizing function): a compact layout of the split
+ * decoder's temp, in which every frame's area is laid out for that frame's own decoded size and placed by an
+ * exclusive scan, and the Huffman job list is sized for the sum of the frames' own block slots, so temp grows with the
+ * batch's total bytes plus a constant per chunk, not with nchunks x (the area of max_chunk_bytes).  A frame of n
+ * bytes takes ceil(n / 128 KiB) + 1 block slots of 8,760 bytes (a block's fields, its sequence tables and its Huffman
+ * table) and n / 4 + 64 sequence records of 8 bytes, 256-aligned (26,368 bytes at 4 KiB, 34,685,184 at 16 MiB), and
+ * as many Huffman job slots as block slots.  The area region is the smaller of nchunks x the area of max_chunk_bytes
+ * and 2 x total_out_bytes + 8,760 x (total_out_bytes / 131072 + 2 x nchunks) + 767 x nchunks; the job list the
+ * smaller of nchunks x the block slots of max_chunk_bytes and total_out_bytes / 131072 + 2 x nchunks jobs.
+ * total_out_bytes: an upper bound of the sum of the decoded sizes over the chunks not larger than max_chunk_bytes (the
+ * promise of total_in_bytes above).  The layout's total (out[22] below) covers every batch of at most nchunks
+ * chunks, each of at most max_chunk_bytes, that sums to at most total_out_bytes; it is non-decreasing in each of the
+ * three and never above lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, nchunks) plus the four per-chunk
+ * arrays (two u32 of nchunks, two u64 of nchunks + 1).  Its own answers:
+ *   4096 chunks, one of 16 MiB and 4095 of 4 KiB (33,550,336 bytes in all):   145,583,104 bytes, where
+ *       lzh_zstd_ragged_decompress_split_temp_bytes answers 142,105,035,776;
+ *   4096 chunks of 128 KiB (536,870,912 bytes in all):   1,149,519,360 bytes against 1,149,420,544 -- a uniform
+ *       batch gains nothing (the same areas and jobs, and the four arrays).
+ * lzh_debug_zstd_ragged_split_compact_layout: the regions as byte ranges, out[2 i], out[2 i + 1] = offset and size
+ * of region i: 0 scanned offsets, 1 the area region, 2 the sequence waves' dummy words, 3 frame states (nchunks x
+ * i32), 4 frame fields, 5 the Huffman jobs' counter, 6 the Huffman jobs, 7 area sizes, 8 job counts (u32 each), 9 area
+ * offsets, 10 job offsets (nchunks + 1 u64 each); out[22] = the total (23 values).  LZH_EARG where
+ * lzh_zstd_ragged_decompress_split_temp_bytes answers 0 (max_chunk_bytes below 16384 or above 16 MiB) or out is null.
+ * lzh_debug_zstd_ragged_split_compact_slots: the placement for a host array of decoded sizes: area_off[i] = the
+ * offset of frame i's area inside the area region, job_off[i] = its first slot in the job list (exclusive scans; a
+ * chunk over max_chunk_bytes takes 0 bytes and 0 slots), in_split[i] = 1 exactly when the chunk is at most
+ * max_chunk_bytes, its area ends inside the area region and its job slots end inside the job list.  LZH_EARG as above,
+ * or for a null pointer with nchunks > 0. */
+int lzh_debug_zstd_ragged_split_compact_slots(const uint64_t* out_sizes, size_t nchunks, size_t max_chunk_bytes,
+                                              size_t total_out_bytes, uint64_t* area_off, uint64_t* job_off,
+                                              uint8_t* in_split);
+int lzh_debug_zstd_ragged_split_compact_layout(size_t total_out_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                               uint64_t* out);
+
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */
 int lzh_compress_kernel_only(int codec, int level, const void* d_in, size_t n, size_t in_readable,

@@ -106,6 +106,8 @@ SIGNATURES = {
     "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
     "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_debug_zstd_ragged_split_compact_slots": (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    "lzh_debug_zstd_ragged_split_compact_layout": (C.c_int, [_SZ, _SZ, _SZ, _P]),
     "lzh_zstd_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
     "lzh_zstd_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),

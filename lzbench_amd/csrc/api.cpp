@@ -528,6 +528,44 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
         });
 }
 
+// ---- 3c, compact layout of the split decoder's temp, debug calls only (no decode call uses it yet): every frame's
+// area laid out for its own size and placed by a scan (zstd_split_slots.h); zstd_ragged_split_compact_temp lays the
+// temp out ----
+int lzh_debug_zstd_ragged_split_compact_layout(size_t total_out_bytes, size_t max_chunk_bytes, size_t nchunks,
+                                               uint64_t* out) {
+    const ZstdRaggedSplitCompactTemp t = zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks);
+    if (!t.ok || !out) return LZH_EARG;
+    const uint64_t v[22] = {t.scan,     (nchunks + 1) * sizeof(uint64_t), t.areas,    t.reg.areas,
+                            t.dummy,    t.dummy_bytes,                    t.state,    t.state_bytes,
+                            t.fields,   t.fields_bytes,                   t.njobs,    4,
+                            t.jobs,     t.jobs_bytes,                     t.area_sz,  nchunks * 4,
+                            t.job_cnt,  nchunks * 4,                      t.area_off, (nchunks + 1) * 8,
+                            t.job_off,  (nchunks + 1) * 8};
+    std::copy(v, v + 22, out);
+    out[22] = t.total;
+    return LZH_OK;
+}
+
+int lzh_debug_zstd_ragged_split_compact_slots(const uint64_t* out_sizes, size_t nchunks, size_t max_chunk_bytes,
+                                              size_t total_out_bytes, uint64_t* area_off, uint64_t* job_off,
+                                              uint8_t* in_split) {
+    const ZstdRaggedSplitCompactTemp t = zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks);
+    if (!t.ok) return LZH_EARG;
+    if (nchunks == 0) return LZH_OK;
+    if (!out_sizes || !area_off || !job_off || !in_split) return LZH_EARG;
+    uint64_t ao = 0, jo = 0;   // (two exclusive scans, then the check of both ends against their regions)
+    for (size_t i = 0; i < nchunks; i++) {
+        const bool over = out_sizes[i] > max_chunk_bytes;
+        const LzhZsplitRegions sz = over ? LzhZsplitRegions{0, 0} : lzh_zstd_split_compact_slot(out_sizes[i]);
+        area_off[i] = ao;
+        job_off[i] = jo;
+        in_split[i] = !over && ao + sz.areas <= t.reg.areas && jo + sz.jobs <= t.reg.jobs;
+        ao += sz.areas;
+        jo += sz.jobs;
+    }
+    return LZH_OK;
+}
+
 // ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h); compact_temp
 // lays the temp out for the sizing call, the async call and the debug calls ----
 size_t lzh_ragged_compact_compress_temp_bytes(int codec, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks) {

@@ -68,6 +68,12 @@ hipError_t lzh_launch_zstd_decompress_ragged_split(const uint8_t* packed, uint64
                                                    void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
                                                    int32_t* status, uint32_t nchunks, const LzhZstdSplitTemp& split,
                                                    hipStream_t s);
+// the compact temp layout of the split decoder (zstd_split_slots.h derives it; host arithmetic for api.cpp's debug
+// calls, no launcher yet): the two regions that hold every batch of at most nchunks frames of at most max_bytes that
+// sums to at most total bytes, and the {area bytes, Huffman job slots} of a frame of n bytes
+struct LzhZsplitRegions { uint64_t areas, jobs; };   // (bytes; Huffman jobs)
+LzhZsplitRegions lzh_zstd_split_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks);
+LzhZsplitRegions lzh_zstd_split_compact_slot(uint64_t n);
 // decode_hip.hip, for the ragged launcher and its layout: the sizes of the split decoder's temp for nchunks frames of
 // up to `chunk` bytes (a frame's area, the dummy words, a frame's fields, a frame's Huffman jobs); the test hooks
 // lzh_debug_zstd_legacy / _hufpar and the Huffman sections a wave (4 or 8: the hook, else by nchunks and the device's

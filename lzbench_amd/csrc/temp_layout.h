@@ -214,3 +214,43 @@ static inline ZstdRaggedSplitTemp zstd_ragged_split_temp(size_t nchunks, size_t 
     t.total = c.at;   // (above ragged_decode_temp's: a frame area alone is over 17 KiB)
     return t;
 }
+
+// ---- the same with the compact layout (zstd_split_slots.h; the debug calls of api.cpp, no decode call yet): every
+// frame's area laid out for the frame's own size and placed by a scan, the job list sized for the frames' own block
+// slots.  The regions of zstd_ragged_split_temp
+// in its order -- the area region and the job list sized by lzh_zstd_split_compact_regions for the promised total,
+// the dummy words a region of their own -- then the placement's four arrays, as compact_arrays lays them out:
+//   scanned offsets | area region | dummy words | frame states | frame fields | the Huffman jobs' counter | jobs
+//   | area sizes | job counts (u32 each) | area offsets | job offsets (nchunks + 1 u64 each)
+// The spare 256 bytes are those of zstd_ragged_split_temp (after the offsets and after the jobs) and the arrays
+// follow without one, so the total never passes that layout's by more than the four arrays.  ok = false (total 0)
+// exactly where zstd_ragged_split_temp's is.
+struct ZstdRaggedSplitCompactTemp {
+    bool ok;
+    LzhZsplitRegions reg;
+    size_t scan, areas, dummy, state, fields, njobs, jobs, area_sz, job_cnt, area_off, job_off, total;
+    size_t dummy_bytes, state_bytes, fields_bytes, jobs_bytes;
+};
+static inline ZstdRaggedSplitCompactTemp zstd_ragged_split_compact_temp(size_t total_out, size_t max_bytes,
+                                                                        size_t nchunks) {
+    ZstdRaggedSplitCompactTemp t = {};
+    t.ok = max_bytes >= lzh_zstd_split_min && max_bytes <= kLz4SplitMax;
+    if (!t.ok) return t;
+    const LzhZstdSplitSizes z = lzh_zstd_split_sizes(max_bytes, nchunks);
+    const size_t job_bytes = lzh_zstd_split_sizes(0, 0).frame_jobs;   // (an empty frame has one block slot: one job)
+    t.reg = lzh_zstd_split_compact_regions(total_out, max_bytes, nchunks);
+    TempCursor c;
+    t.scan = c.take((nchunks + 1) * sizeof(uint64_t), kGap);
+    t.areas = c.take(t.reg.areas);
+    t.dummy = c.take(t.dummy_bytes = z.dummy);
+    t.state = c.take(t.state_bytes = nchunks * 4);
+    t.fields = c.take(t.fields_bytes = nchunks * z.frame_fields);
+    t.njobs = c.take(4);
+    t.jobs = c.take(t.jobs_bytes = t.reg.jobs * job_bytes, kGap);
+    t.area_sz = c.take(nchunks * 4);
+    t.job_cnt = c.take(nchunks * 4);
+    t.area_off = c.take((nchunks + 1) * 8);
+    t.job_off = c.take((nchunks + 1) * 8);
+    t.total = c.at;
+    return t;
+}

@@ -137,6 +137,15 @@ lzh_zstd_decompress_ragged_sel_kernel(const uint8_t* packed, uint64_t packed_rea
 }
 
 #include "launch.h"
+#include "zstd_split_slots.h"
+
+// the area arithmetic of the compact temp layout (zstd_split_slots.h) for api.cpp, which cannot include
+// decode_hip.hip, where the layout it derives from (zsplit::zlayout) lives: the two regions, and the area and job
+// slots of a frame of n bytes.  Host arithmetic only; no kernel decodes through that layout yet.
+LzhZsplitRegions lzh_zstd_split_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
+    return lzh_zsplit_regions(total, max_bytes, nchunks);
+}
+LzhZsplitRegions lzh_zstd_split_compact_slot(uint64_t n) { return {lzh_zsplit_area_bytes(n), lzh_zsplit_jobs(n)}; }
 
 // Every launch on s, in the order of the uniform launcher with everything on one stream: the job counter's memset,
 // header, Huffman streams a lane each (4 or 8 sections a wave), long streams a wave each, sequences, execution, then
