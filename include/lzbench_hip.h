@@ -348,6 +348,45 @@ int lzh_debug_zstd_ragged_compact_slots(int level, const uint64_t* sizes, size_t
 int lzh_debug_zstd_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes, size_t nchunks,
                                           uint64_t* out);
 
+/* ---- 3d. LZ4 ragged batches with a shared dictionary ------------------------------------- */
+/* lzh_compress_ragged_async / lzh_decompress_ragged_async for LZ4 with one dictionary shared by every chunk of the
+ * batch: what LZ4_loadDict + LZ4_compress_fast_continue and LZ4_decompress_safe_usingDict do for small records
+ * (256 bytes to some KiB), which alone find little to match.  The contract is that of 3b -- device arrays of nchunks
+ * entries, any alignment, chunks may overlap or repeat, 16 readable bytes after every input chunk, nchunks == 0
+ * returns LZH_OK and launches nothing, a chunk larger than max_chunk_bytes is not processed (d_csizes[i] = 0 /
+ * d_status[i] = -1), packed_cap enforced on the device, d_offsets of the decompress call may be NULL, the raw-store
+ * rule on both sides, the packed layout (d_csizes, d_offsets[0 .. nchunks], chunks contiguous in index order: the
+ * scan and the pack are those of lzh_compress_ragged_async) -- but for the dictionary arguments and the limits:
+ *   d_dict, dict_bytes: the dictionary, one device buffer of any alignment with 16 readable bytes after it;
+ *       8 <= dict_bytes <= 65536, else LZH_EARG (below 8 bytes LZ4_loadDict loads nothing; a longer dictionary is
+ *       the caller's to cut to its last 64 KiB, as LZ4_loadDict does);
+ *   max_chunk_bytes <= 4 MiB, else LZH_EARG.
+ * The sizing functions return 0 exactly where the calls return LZH_EARG for those arguments; they are host
+ * arithmetic and non-decreasing in every argument.  Check order: arguments, nchunks == 0, null pointers (d_dict
+ * among them), then temp_bytes below the sizing answer: LZH_ESPACE; all before any device call.
+ * Compressed bytes: chunk i is exactly what lz4 1.9.3 writes for it when the dictionary lies directly before the
+ * chunk in one buffer, a fresh LZ4_stream_t gets LZ4_loadDict(stream, dict, dict_bytes), and
+ * LZ4_compress_fast_continue(stream, chunk, dst, n, LZ4_compressBound(n), acc) runs, acc = level (level <= 1: 1).
+ * Decoding: d_status[i] and the bytes are those of LZ4_decompress_safe_usingDict(src, dst, csize, d_out_bytes[i],
+ * dict, dict_bytes): the decoded size, or negative where the reference returns negative; an offset may reach
+ * dict_bytes before the chunk's first byte, one more is an error; blocks written without a dictionary decode as
+ * before.
+ * Temp: nchunks staging slots of lzh_stage_stride(LZH_CODEC_LZ4, max_chunk_bytes) and the dictionary's hash table
+ * (16 KiB, built once per call) for compression -- never above lzh_ragged_compress_temp_bytes(LZH_CODEC_LZ4, ..)
+ * + 64 KiB + 64 bytes a chunk, and no copy of the dictionary; the scanned offsets for decompression.
+ * Streams: every launch goes on hip_stream; no side stream, event, host synchronisation or size read back. */
+size_t lzh_lz4_dict_compress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_lz4_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks);
+int lzh_lz4_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes,
+                                       const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                       size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                       uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream);
+int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
+                                         size_t packed_readable, const uint32_t* d_csizes, const uint64_t* d_offsets,
+                                         void* const* d_out_ptrs, const uint64_t* d_out_bytes, size_t nchunks,
+                                         size_t max_chunk_bytes, int32_t* d_status, void* d_temp, size_t temp_bytes,
+                                         void* hip_stream);
+
 /* Debug only, host arithmetic only (they may change; no decode call takes this layout yet, so the split decoder runs
  * with the uniform-slot temp above alone and there is no public sizing function): a compact layout of the split
  * decoder's temp, in which every frame's area is laid out for that frame's own decoded size and placed by an

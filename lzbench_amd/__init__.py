@@ -116,6 +116,10 @@ SIGNATURES = {
     "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
+    "lzh_lz4_dict_compress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "lzh_lz4_dict_decompress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "lzh_lz4_compress_ragged_dict_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_lz4_decompress_ragged_dict_async": (C.c_int, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_compress_kernel_only": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_kernel_stage": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
@@ -406,12 +410,17 @@ class RaggedCodec:
     (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
     batches); where there is none (max_chunk_bytes below 16 KiB) the temp stays the small one and every frame
     decodes in the one-wave kernel, as with split_decode=False.
+    dictionary=<uint8 tensor of 8 .. 65536 bytes> (lz4 / lz4fast without compact, else ValueError; chunks up to
+    4 MiB) shares one LZ4 dictionary among all chunks (include/lzbench_hip.h 3d): compress() writes what
+    LZ4_loadDict + LZ4_compress_fast_continue write for each chunk, decompress() is LZ4_decompress_safe_usingDict.
+    The tensor is copied once (self.dictionary); small records that share content with it compress several times
+    smaller than alone.
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
     def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
                  max_total_bytes: Optional[int] = None, compact: bool = False, split_decode: bool = False,
-                 compact_scratch: bool = False):
+                 compact_scratch: bool = False, dictionary=None):
         import torch
         self.torch = torch
         self.codec = CODECS[codec]
@@ -429,6 +438,9 @@ class RaggedCodec:
         if split_decode and not self.zstd:
             raise ValueError("ragged batches: split_decode is a zstd option")
         self.split_decode = split_decode
+        if dictionary is not None and (codec != "lz4" and codec != "lz4fast" or compact):
+            raise ValueError("ragged batches: a dictionary goes with codec lz4 / lz4fast and the uniform-slot layout "
+                             "(compact=False)")
         # the variant, chosen once: the compress and decompress calls (their names go into the error texts), each with
         # the arguments it takes before the chunk arrays, and the sizing call; the compact layouts take the batch's
         # total too (sizing: after the codec or level; compress: after max_chunk_bytes, and max_total as it is then:
@@ -441,12 +453,26 @@ class RaggedCodec:
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
             if split_decode:   # (0: no split decoder for chunks of this size)
                 dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
+        elif dictionary is not None:   # (3d: the dictionary's own calls; it is kept with 16 readable bytes after it)
+            nd = int(dictionary.numel())
+            ct = L.lzh_lz4_dict_compress_temp_bytes(nd, max_chunk_bytes, max_chunks)
+            dt = L.lzh_lz4_dict_decompress_temp_bytes(nd, max_chunk_bytes, max_chunks)
+            if ct == 0 or dt == 0:
+                raise ValueError(f"ragged batches: a dictionary of {nd} bytes (8 .. 65536) / chunks of {max_chunk_bytes} "
+                                 "bytes (up to 4 MiB) are not supported")
+            dev = device or torch.device("cuda", torch.cuda.current_device())
+            self.dictionary = torch.zeros(nd + 16, dtype=torch.uint8, device=dev)
+            self.dictionary[:nd].copy_(dictionary.reshape(-1))
+            self._compress, self._decompress = L.lzh_lz4_compress_ragged_dict_async, L.lzh_lz4_decompress_ragged_dict_async
+            self._chead, self._dhead = (self.level, self.dictionary.data_ptr(), nd), (self.dictionary.data_ptr(), nd)
+            sizing = None
         else:
             self._compress = L.lzh_compress_ragged_compact_async if compact else L.lzh_compress_ragged_async
             sizing = L.lzh_ragged_compact_compress_temp_bytes if compact else L.lzh_ragged_compress_temp_bytes
             self._chead, self._decompress, self._dhead = (self.codec, self.level), L.lzh_decompress_ragged_async, (self.codec,)
             dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
-        ct = sizing(self._chead[0], *((self.max_total,) if self._promise else ()), max_chunk_bytes, max_chunks)
+        if sizing is not None:
+            ct = sizing(self._chead[0], *((self.max_total,) if self._promise else ()), max_chunk_bytes, max_chunks)
         if ct == 0 or dt == 0:
             raise ValueError(f"ragged batches: codec {codec} (level {self.level}) / chunks of {max_chunk_bytes} bytes "
                              "are not supported")

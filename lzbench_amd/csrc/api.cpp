@@ -437,6 +437,59 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
         });
 }
 
+// ---- 3d. LZ4 ragged batches with a shared dictionary: lz4_dict_temp / ragged_decode_temp, the checks and the
+// scan -> pack of 3b ----
+static bool lz4_dict_ok(size_t dict_bytes, size_t max_chunk_bytes) {
+    return dict_bytes >= 8 && dict_bytes <= 65536 && max_chunk_bytes <= kLz4DictMax;
+}
+
+size_t lzh_lz4_dict_compress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    return lz4_dict_ok(dict_bytes, max_chunk_bytes) ? lz4_dict_temp(nchunks, max_chunk_bytes).total : 0;
+}
+
+size_t lzh_lz4_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    return lz4_dict_ok(dict_bytes, max_chunk_bytes) ? ragged_decode_temp(nchunks).total : 0;
+}
+
+int lzh_lz4_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes,
+                                       const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                       size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                       uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const DictTemp t = lz4_dict_temp(nchunks, max_chunk_bytes);
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    const int acc = level < 1 ? 1 : std::min(level, 65537);   // (LZ4_ACCELERATION_MAX, lz4.c:1578)
+    return ragged_compress(
+        lz4_dict_ok(dict_bytes, max_chunk_bytes), nchunks,
+        d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes,
+        d_csizes, d_offsets, s,
+        [&] {
+            return lzh_launch_lz4_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, (uint32_t*)(base + t.tab), d_in_ptrs,
+                                       d_in_bytes, max_chunk_bytes, acc, base + t.stage, t.stride, d_csizes, k, s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
+}
+
+int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
+                                         size_t packed_readable, const uint32_t* d_csizes, const uint64_t* d_offsets,
+                                         void* const* d_out_ptrs, const uint64_t* d_out_bytes, size_t nchunks,
+                                         size_t max_chunk_bytes, int32_t* d_status, void* d_temp, size_t temp_bytes,
+                                         void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return ragged_decompress(
+        lz4_dict_ok(dict_bytes, max_chunk_bytes), nchunks,
+        d_dict && d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp,
+        temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+            return lzh_launch_lz4_dict_decompress((const uint8_t*)d_dict, (uint32_t)dict_bytes, (const uint8_t*)d_packed,
+                                                  packed_readable, offs, d_csizes, d_out_ptrs, d_out_bytes,
+                                                  max_chunk_bytes, d_status, (uint32_t)nchunks, s);
+        });
+}
+
 // ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
 // compress temp: chunk_temp(zstd) of nchunks staging slots and scratch areas sized for max_chunk_bytes;
 // decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors), or

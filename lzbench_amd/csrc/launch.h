@@ -133,6 +133,18 @@ hipError_t lzh_launch_ragged_desc(const uint64_t* offsets, const uint32_t* csize
                                   const uint64_t* out_bytes, uint64_t max_bytes, void* desc, int32_t* status,
                                   uint32_t nchunks, hipStream_t s);
 
+// LZ4 ragged batches with a shared dictionary (lz4_dict_hip.hip; include/lzbench_hip.h 3d): dict_bytes in 8 .. 65536,
+// 16 readable bytes after the dictionary; tab: 4096 u32 of temp for LZ4_loadDict's table, built by the call; staging
+// slots of `stride` as above, no records.  Every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 /
+// status[i] = -1.
+hipError_t lzh_launch_lz4_dict(const uint8_t* dict, uint32_t dict_bytes, uint32_t* tab, const void* const* in_ptrs,
+                               const uint64_t* in_bytes, uint64_t max_bytes, int acc, uint8_t* stage, uint64_t stride,
+                               uint32_t* csizes, uint32_t nchunks, hipStream_t s);
+hipError_t lzh_launch_lz4_dict_decompress(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed,
+                                          uint64_t packed_readable, const uint64_t* offsets, const uint32_t* csizes,
+                                          void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
+                                          int32_t* status, uint32_t nchunks, hipStream_t s);
+
 // the compact layout of a ragged compression (ragged_compact_hip.hip, ragged_slots.h): chunk i's staging slot is
 // stage_sz[i] bytes at stage_off[i] of a staging region of stage_cap bytes, its record slot rec_sz[i] bytes at
 // rec_off[i] of a record region of rec_cap bytes (device arrays: nchunks u32, nchunks + 1 u64).

@@ -58,6 +58,21 @@ static inline ChunkTemp chunk_temp(int codec, size_t k, size_t chunk) {
     return t;
 }
 
+// ---- LZ4 compression of k chunks of up to `chunk` bytes with a shared dictionary (3d): the staging slots of
+// chunk_temp, then LZ4_loadDict's table (4096 u32).  No records (the parse emits in-kernel) and no copy of the
+// dictionary: below chunk_temp(LZH_CODEC_LZ4, k, chunk) but for the table.
+static const size_t kLz4DictMax = (size_t)4 << 20;      // largest chunk of the dictionary calls
+struct DictTemp { size_t stride, stage, tab, total; };
+static inline DictTemp lz4_dict_temp(size_t k, size_t chunk) {
+    DictTemp t;
+    TempCursor c;
+    t.stride = lzh_stage_stride(LZH_CODEC_LZ4, chunk);
+    t.stage = c.take(k * t.stride, kGap);
+    t.tab = c.take(4096 * sizeof(uint32_t), kGap);
+    t.total = c.at;
+    return t;
+}
+
 // ---- framed compression: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes:
 //   staging slots | LZ4 sequence records of the blocks, then 8 bytes per block (linked frames: the per-frame
 //   table snapshots instead) | block sizes | block offsets inside their frame
