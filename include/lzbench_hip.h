@@ -60,8 +60,22 @@ extern "C" {
  * row, nvcomp/LZ4Metadata.h), LZ4 blocks of 1 << (15 + level) bytes, level 0..5 (compressors.cpp:1863).
  * Both: lzh_compress_async / lzh_decompress_async and the rows below; not lzh_compress_kernel_only /
  * lzh_compress_finish_async. */
+/* LZH_CODEC_ZSTD_DFAST: zstd 1.5.2 frames at the levels whose ZSTD_getParams row is ZSTD_dfast (double-fast) for
+ * every chunk size: level 3, zstd's own default (clevels.h:25-111: dfast in all four source-size tables).  Same
+ * frame shape as LZH_CODEC_ZSTD, bit-exact with the reference; every other level returns LZH_EARG (level 2 is fast
+ * in two tables and dfast in one, level 4 greedy in two: neither is one code path for a batch).  LZH_CODEC_ZSTD
+ * itself keeps refusing level 3.
+ * With this codec: lzh_stage_stride and lzh_max_packed_bytes equal LZH_CODEC_ZSTD's; lzh_compress_temp_bytes sizes
+ * the per-frame scratch with the two dfast tables (long 4 << hashLog + short 4 << chainLog bytes: 768 KiB a frame
+ * for chunks over 256 KiB, 192 KiB at 16 KiB) and is never below LZH_CODEC_ZSTD's; lzh_compress_async takes chunk
+ * sizes up to 16 MiB (larger: LZH_EARG) and checks in the uniform call's order (arguments, temp_bytes and
+ * packed_cap: LZH_ESPACE, then level and chunk size: LZH_EARG), every launch on hip_stream (no side stream: a
+ * captured call has no parallel branches); lzh_decompress_temp_bytes and lzh_decompress_async are LZH_CODEC_ZSTD's
+ * (the frames also decode with LZH_CODEC_ZSTD).  lzh_compress_kernel_only, lzh_compress_kernel_stage,
+ * lzh_compress_finish_async, the ragged calls (3b) return LZH_EARG for it and their temp sizing functions 0; the
+ * ragged zstd calls (3c) keep refusing level 3, and the dictionary calls (3d) are LZ4's. */
 enum { LZH_CODEC_LZ4 = 0, LZH_CODEC_SNAPPY = 1, LZH_CODEC_MEMCPY = 2, LZH_CODEC_ZSTD = 3, LZH_CODEC_LZ4F = 4,
-       LZH_CODEC_NVLZ4 = 5 };
+       LZH_CODEC_NVLZ4 = 5, LZH_CODEC_ZSTD_DFAST = 6 };
 #define LZH_LZ4F_BLOCK_CHECKSUM   0x10   /* LZ4F_blockChecksumEnabled */
 #define LZH_LZ4F_CONTENT_CHECKSUM 0x20   /* LZ4F_contentChecksumEnabled */
 #define LZH_LZ4F_CONTENT_SIZE     0x40   /* frameInfo.contentSize = chunk size */
@@ -74,6 +88,7 @@ char*   lzbench_hip_lz4_init(size_t chunk_size, size_t level, size_t ngpus);
 char*   lzbench_hip_snappy_init(size_t chunk_size, size_t level, size_t ngpus);
 char*   lzbench_hip_memcpy_init(size_t chunk_size, size_t level, size_t ngpus);
 char*   lzbench_hip_zstd_init(size_t chunk_size, size_t level, size_t ngpus);
+char*   lzbench_hip_zstd_dfast_init(size_t chunk_size, size_t level, size_t ngpus);
 char*   lzbench_hip_lz4frame_init(size_t chunk_size, size_t level, size_t ngpus);
 char*   lzbench_hip_nvcomp_lz4_init(size_t chunk_size, size_t level, size_t ngpus);
 void    lzbench_hip_deinit(char* workmem);
@@ -87,6 +102,9 @@ int64_t lzbench_hip_snappy_decompress(char* in, size_t insize, char* out, size_t
  * zstd / zstd_fast rows pass it (size_t of a possibly negative int) */
 int64_t lzbench_hip_zstd_compress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t p2, char* workmem);
 int64_t lzbench_hip_zstd_decompress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t p2, char* workmem);
+/* zstd level 3 (LZH_CODEC_ZSTD_DFAST, workmem from lzbench_hip_zstd_dfast_init): level must be 3.  Decompression is
+ * lzbench_hip_zstd_decompress, which takes a workmem of either zstd init */
+int64_t lzbench_hip_zstd_dfast_compress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t p2, char* workmem);
 /* LZ4 frame per chunk: level = LZH_LZ4F_PARAMS(...): 4..7 = blockSizeID 64 KiB .. 4 MiB without flags,
  * e.g. 0x74 = 64 KiB blocks + block / content checksums + content size */
 int64_t lzbench_hip_lz4frame_compress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t p2, char* workmem);
@@ -119,7 +137,8 @@ size_t lzh_num_chunks(size_t n, size_t chunk_size);
 /* 1 when the GPU codec compresses at `level` for chunks of up to chunk_size bytes, else 0 (the
  * rows and lzh_compress_async then return LZH_EARG): zstd at the levels whose ZSTD_getParams row
  * is the fast strategy for every chunk size up to chunk_size (lzbench's zstd level 2 is double-fast
- * above 256 KiB: compressors.cpp:1752 via clevels.h); LZ4F / nvcomp at the parameters above. */
+ * above 256 KiB: compressors.cpp:1752 via clevels.h); LZH_CODEC_ZSTD_DFAST at level 3 alone, for any chunk_size;
+ * LZ4F / nvcomp at the parameters above. */
 int lzh_level_supported(int codec, int level, size_t chunk_size);
 /* The batched rows' sharding plan (api.cpp make_plan) and per-shard buffer sizes for n bytes in
  * chunks of chunk_size over ngpus shards, into out[0 .. nout): chunks, chunks per sub-batch,

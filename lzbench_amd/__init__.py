@@ -24,6 +24,7 @@ __all__ = [
     "ExtensionMissing", "lib", "CODECS", "COMP_DESC", "CompressorDesc", "find_compressor",
     "compress_chunks", "decompress_chunks", "chunk_sizes_for", "datagen", "DeviceCodec", "RaggedCodec",
     "LZH_CODEC_LZ4", "LZH_CODEC_SNAPPY", "LZH_CODEC_MEMCPY", "LZH_CODEC_ZSTD", "LZH_CODEC_LZ4F", "LZH_CODEC_NVLZ4",
+    "LZH_CODEC_ZSTD_DFAST",
     "LZ4F_BLOCK_CHECKSUM", "LZ4F_CONTENT_CHECKSUM", "LZ4F_CONTENT_SIZE", "LZ4F_LINKED", "PAD_SIZE",
     "get_compress_bound",
 ]
@@ -34,13 +35,14 @@ LIB_PATH = os.environ.get("LZH_LIB") or os.path.join(_HERE, "liblzbench_hip.so")
 DATAGEN_PATH = os.path.join(_HERE, "libdatagen.so")
 
 LZH_CODEC_LZ4, LZH_CODEC_SNAPPY, LZH_CODEC_MEMCPY, LZH_CODEC_ZSTD, LZH_CODEC_LZ4F, LZH_CODEC_NVLZ4 = 0, 1, 2, 3, 4, 5
+LZH_CODEC_ZSTD_DFAST = 6      # zstd level 3 (the double-fast strategy): LZH_CODEC_ZSTD's frames, a codec of its own
 CODECS = {"lz4": LZH_CODEC_LZ4, "lz4fast": LZH_CODEC_LZ4, "snappy": LZH_CODEC_SNAPPY, "memcpy": LZH_CODEC_MEMCPY,
           "zstd": LZH_CODEC_ZSTD, "zstd_fast": LZH_CODEC_ZSTD, "lz4frame": LZH_CODEC_LZ4F,
-          "nvcomp_lz4": LZH_CODEC_NVLZ4}
+          "nvcomp_lz4": LZH_CODEC_NVLZ4, "zstd_dfast": LZH_CODEC_ZSTD_DFAST}
 # LZ4 frame parameters (include/lzbench_hip.h LZH_LZ4F_*): level = bsid | flags | acceleration << 8
 LZ4F_BLOCK_CHECKSUM, LZ4F_CONTENT_CHECKSUM, LZ4F_CONTENT_SIZE, LZ4F_LINKED = 0x10, 0x20, 0x40, 0x80
 # codecs whose level is passed through as is (the others: 1 for lz4 = LZ4_compress_default, 0)
-_LEVELED = ("lz4fast", "zstd", "zstd_fast", "lz4frame", "nvcomp_lz4")
+_LEVELED = ("lz4fast", "zstd", "zstd_fast", "zstd_dfast", "lz4frame", "nvcomp_lz4")
 PAD_SIZE = 16 * 1024          # lzbench.h:14
 
 
@@ -67,6 +69,8 @@ SIGNATURES = {
     "lzbench_hip_snappy_init": (_P, [_SZ, _SZ, _SZ]),
     "lzbench_hip_memcpy_init": (_P, [_SZ, _SZ, _SZ]),
     "lzbench_hip_zstd_init": (_P, [_SZ, _SZ, _SZ]),
+    "lzbench_hip_zstd_dfast_init": (_P, [_SZ, _SZ, _SZ]),
+    "lzbench_hip_zstd_dfast_compress": _COMPRESS_FUNC,
     "lzbench_hip_lz4frame_init": (_P, [_SZ, _SZ, _SZ]),
     "lzbench_hip_nvcomp_lz4_init": (_P, [_SZ, _SZ, _SZ]),
     "lzbench_hip_lz4frame_compress": _COMPRESS_FUNC,
@@ -209,6 +213,10 @@ COMP_DESC = (
     CompressorDesc("hip_zstd_fast", "1.5.2", -5, -1, 1, 0, "lzbench_hip_zstd_compress", "lzbench_hip_zstd_decompress",
                    "lzbench_hip_zstd_init", "lzbench_hip_deinit",
                    "lzbench_hip_compress_batch", "lzbench_hip_decompress_batch"),
+    # zstd's default level: the double-fast strategy, a codec of its own (LZH_CODEC_ZSTD_DFAST); same frames
+    CompressorDesc("hip_zstd_dfast", "1.5.2", 3, 3, 1, 0, "lzbench_hip_zstd_dfast_compress",
+                   "lzbench_hip_zstd_decompress", "lzbench_hip_zstd_dfast_init", "lzbench_hip_deinit",
+                   "lzbench_hip_compress_batch", "lzbench_hip_decompress_batch"),
     # framed formats: an LZ4 frame per chunk (level = LZH_LZ4F_PARAMS), the nvcomp_lz4 row's container
     # (lzbench.h:218, levels 0..5 = chunks of 32 KiB << level)
     CompressorDesc("hip_lz4frame", "1.9.3", 4, 7, 1, 0, "lzbench_hip_lz4frame_compress",
@@ -250,7 +258,8 @@ class _Row:
 
     def __init__(self, codec: str, chunk_size: int, level: int = 0, ngpus: int = 1):
         L = lib()
-        base = {"memcpy": "memcpy", "snappy": "snappy", "zstd": "zstd", "zstd_fast": "zstd", "lz4frame": "lz4frame",
+        base = {"memcpy": "memcpy", "snappy": "snappy", "zstd": "zstd", "zstd_fast": "zstd", "zstd_dfast": "zstd_dfast",
+                "lz4frame": "lz4frame",
                 "nvcomp_lz4": "nvcomp_lz4"}.get(codec, "lz4")
         self.desc = find_compressor("hipMemcpy" if codec == "memcpy" else codec)
         self.wm = getattr(L, f"lzbench_hip_{base}_init")(chunk_size, level, ngpus)

@@ -48,7 +48,7 @@ extern "C" size_t lzb_datagen(int kind, uint64_t seed, uint8_t* buf, size_t n);
 
 extern "C" {
 
-const char* lzh_version(void) { return "lzbench_hip 0.2 (lz4 1.9.3 / snappy 1.1.8 / zstd 1.5.2 fast levels bit-exact, gfx950)"; }
+const char* lzh_version(void) { return "lzbench_hip 0.2 (lz4 1.9.3 / snappy 1.1.8 / zstd 1.5.2 fast levels + level 3 bit-exact, gfx950)"; }
 
 size_t lzh_datagen(int kind, uint64_t seed, void* buf, size_t n) { return lzb_datagen(kind, seed, (uint8_t*)buf, n); }
 
@@ -66,7 +66,7 @@ static size_t codec_bound(int codec, size_t part) {
         return part + part / 255 + 24 * ((part + 32767) / 32768) + 48;
     if (codec == LZH_CODEC_LZ4) return part + part / 255 + 16;     // LZ4_compressBound, lz4.h:171
     if (codec == LZH_CODEC_SNAPPY) return 32 + part + part / 6;    // MaxCompressedLength, snappy.cc:99-121
-    if (codec == LZH_CODEC_ZSTD)                                    // ZSTD_COMPRESSBOUND, zstd.h:~210
+    if (codec == LZH_CODEC_ZSTD || codec == LZH_CODEC_ZSTD_DFAST)   // ZSTD_COMPRESSBOUND, zstd.h:~210
         return part + (part >> 8) + (part < (128u << 10) ? ((128u << 10) - part) >> 11 : 0);
     return part;
 }
@@ -91,6 +91,7 @@ static bool frame_level_ok(int codec, int level) {
 
 extern "C" int lzh_level_supported(int codec, int level, size_t chunk_size) {
     if (codec == LZH_CODEC_ZSTD) return lzh_zstd_level_ok(level, chunk_size) ? 1 : 0;
+    if (codec == LZH_CODEC_ZSTD_DFAST) return level == 3 ? 1 : 0;   // (dfast in all four clevels tables)
     if (codec == LZH_CODEC_LZ4F || codec == LZH_CODEC_NVLZ4) return frame_level_ok(codec, level) ? 1 : 0;
     return codec >= LZH_CODEC_LZ4 && codec <= LZH_CODEC_MEMCPY ? 1 : 0;
 }
@@ -111,7 +112,12 @@ size_t lzh_compress_temp_bytes(int codec, size_t n, size_t chunk_size) {
     return chunk_temp(codec, lzh_num_chunks(n, chunk_size), chunk_size).total;
 }
 
-size_t lzh_decompress_temp_bytes(int codec, size_t n, size_t chunk_size) { return decode_temp(codec, n, chunk_size).total; }
+// (LZH_CODEC_ZSTD_DFAST writes LZH_CODEC_ZSTD's frames: one decoder)
+static int decode_codec(int codec) { return codec == LZH_CODEC_ZSTD_DFAST ? LZH_CODEC_ZSTD : codec; }
+
+size_t lzh_decompress_temp_bytes(int codec, size_t n, size_t chunk_size) {
+    return decode_temp(decode_codec(codec), n, chunk_size).total;
+}
 
 int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* d_in, size_t n, size_t in_readable,
                               size_t chunk_size, void* d_stage, uint32_t* d_csizes, void* hip_stream) {
@@ -221,6 +227,29 @@ int lzh_compress_async(int codec, int level, const void* d_in, size_t n, size_t 
                                         (uint32_t)g.nblocks, (uint32_t)g.nframes, s));
         return LZH_OK;
     }
+    if (codec == LZH_CODEC_ZSTD_DFAST) {   // match + entropy per block index -> scan -> pack, every launch on s
+        if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
+        if (level != 3 || chunk_size > kLz4SplitMax) return LZH_EARG;
+        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
+        uint8_t* base = (uint8_t*)d_temp;
+        {
+            Range range("lzh:compress_kernel");
+            LZH_CHECK(lzh_launch_zstd_dfast_compress((const uint8_t*)d_in, n, in_readable, chunk_size, level,
+                                                     base + t.stage, t.stride, d_csizes, (uint32_t)k, base + t.recs, s));
+        }
+        Range range("lzh:scan_pack");
+        LZH_CHECK(lzh_launch_scan(d_csizes, k, d_offsets, nullptr, s));
+        if (n == 0) {
+            // (the pack kernel looks chunks up in the input and finds none in an empty one: the one frame of an empty
+            // input -- magic, descriptor, a content size of 0, an empty last raw block -- is copied as it is)
+            const size_t kEmptyFrame = 4 + 1 + 1 + 3;
+            LZH_CHECK(lzh_launch_memcpy(base + t.stage, d_packed, kEmptyFrame, s));
+            return LZH_OK;
+        }
+        LZH_CHECK(lzh_launch_pack((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage, t.stride, d_csizes,
+                                  d_offsets, (uint8_t*)d_packed, packed_cap, (uint32_t)k, s));
+        return LZH_OK;
+    }
     int rc = lzh_compress_kernel_only(codec, level, d_in, n, in_readable, chunk_size, d_temp, d_csizes, hip_stream);
     if (rc) return rc;
     return lzh_compress_finish_async(codec, d_in, n, in_readable, chunk_size, d_temp, d_csizes, d_packed, packed_cap,
@@ -249,6 +278,7 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
                          void* d_temp, size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     if (!chunk_size || !d_csizes || !d_status || (n && (!d_out || !d_packed))) return LZH_EARG;
+    codec = decode_codec(codec);
     if (codec < 0 || codec > LZH_CODEC_NVLZ4) return LZH_EARG;
     if (codec == LZH_CODEC_ZSTD && chunk_size > (1u << 30)) return LZH_EARG;
     const size_t k = lzh_num_chunks(n, chunk_size);
@@ -1157,6 +1187,7 @@ char* lzbench_hip_lz4_init(size_t chunk_size, size_t level, size_t ngpus) { (voi
 char* lzbench_hip_snappy_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_SNAPPY, chunk_size, ngpus); }
 char* lzbench_hip_memcpy_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_MEMCPY, chunk_size, ngpus); }
 char* lzbench_hip_zstd_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_ZSTD, chunk_size, ngpus); }
+char* lzbench_hip_zstd_dfast_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_ZSTD_DFAST, chunk_size, ngpus); }
 char* lzbench_hip_lz4frame_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_LZ4F, chunk_size, ngpus); }
 char* lzbench_hip_nvcomp_lz4_init(size_t chunk_size, size_t level, size_t ngpus) { (void)level; return ctx_new(LZH_CODEC_NVLZ4, chunk_size, ngpus); }
 
@@ -1184,7 +1215,13 @@ int64_t lzbench_hip_zstd_compress(char* in, size_t insize, char* out, size_t out
     return one_chunk_compress(LZH_CODEC_ZSTD, in, insize, out, outsize, level, wm);
 }
 int64_t lzbench_hip_zstd_decompress(char* in, size_t insize, char* out, size_t outsize, size_t, size_t, char* wm) {
-    return one_chunk_decompress(LZH_CODEC_ZSTD, in, insize, out, outsize, wm);
+    // (a workmem of either zstd init: the level-3 codec writes the same frames)
+    const LzhCtx* c = ctx_of(wm);
+    const int codec = c && c->codec == LZH_CODEC_ZSTD_DFAST ? LZH_CODEC_ZSTD_DFAST : LZH_CODEC_ZSTD;
+    return one_chunk_decompress(codec, in, insize, out, outsize, wm);
+}
+int64_t lzbench_hip_zstd_dfast_compress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t, char* wm) {
+    return one_chunk_compress(LZH_CODEC_ZSTD_DFAST, in, insize, out, outsize, level, wm);
 }
 int64_t lzbench_hip_lz4frame_compress(char* in, size_t insize, char* out, size_t outsize, size_t level, size_t, char* wm) {
     return one_chunk_compress(LZH_CODEC_LZ4F, in, insize, out, outsize, level, wm);

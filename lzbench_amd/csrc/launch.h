@@ -42,6 +42,15 @@ size_t lzh_zstd_scratch_stride(size_t chunk_size, int level);
 int lzh_zstd_level_ok(int level, size_t chunk_size);
 // dynamic LDS of the zstd match kernels for frames of up to chunk_size bytes (0: the hash table lives in scratch)
 uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size);
+// zstd level 3, the double-fast strategy (zstdc_dfast_hip.hip; LZH_CODEC_ZSTD_DFAST): staging slots as for
+// lzh_launch_zstd_compress, per-frame scratch areas of lzh_zstd_dfast_scratch_stride(chunk_size) -- the fast levels'
+// areas below the table, then the long and the short table, each the largest of any chunk size up to chunk_size.
+// One match / entropy pair per block index, every launch on s: no side stream, so a captured call has no parallel
+// branches.
+hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
+                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                          uint8_t* scratch, hipStream_t s);
+size_t lzh_zstd_dfast_scratch_stride(size_t chunk_size);
 // ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip, zstd_ragged_split_hip.hip;
 // include/lzbench_hip.h 3c): chunk i = in_bytes[i] bytes at in_ptrs[i]; staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes)
 // lays them out (fstride: its rec_stride, the scratch areas' distance, at least lzh_zstd_scratch_stride(max_bytes,

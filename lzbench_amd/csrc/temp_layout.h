@@ -35,6 +35,11 @@ static const size_t kGap = 256;
 //   k staging slots of `stride` | split (LZ4 / snappy up to kLz4SplitMax): k record slots of `rec_stride` at
 //   `recs`, then the per-chunk record counts at `hdr` (LZ4: 8 bytes a chunk; snappy: a u32 per fragment)
 //                               | zstd: k per-frame scratch areas of the two zstd kernels at `recs`, worst level
+//                               | zstd level 3 (LZH_CODEC_ZSTD_DFAST): the same with that codec's own scratch stride
+// per-frame scratch of the level-3 codec: the fast levels' areas below the table (the zstd kernels' Layout), then
+// the long and the short table, each the largest of any chunk size up to `chunk` (zstdc_dfast_hip.hip computes it)
+static inline size_t zstd_dfast_scratch_stride(size_t chunk) { return lzh_zstd_dfast_scratch_stride(chunk); }
+
 struct ChunkTemp {
     bool split;
     size_t stride, rec_stride, stage, recs, hdr, total;
@@ -52,6 +57,9 @@ static inline ChunkTemp chunk_temp(int codec, size_t k, size_t chunk) {
         t.hdr = c.take(codec == LZH_CODEC_LZ4 ? k * 8 : k * 4 * lzh_snappy_ragged_frags(chunk), kGap);
     } else if (codec == LZH_CODEC_ZSTD) {
         for (int lv : {1, 2, -1, -2}) t.rec_stride = std::max(t.rec_stride, lzh_zstd_scratch_stride(chunk, lv));
+        t.recs = c.take_sized(k * t.rec_stride + kGap);
+    } else if (codec == LZH_CODEC_ZSTD_DFAST) {
+        t.rec_stride = zstd_dfast_scratch_stride(chunk);
         t.recs = c.take_sized(k * t.rec_stride + kGap);
     }
     t.total = c.at;

@@ -1,0 +1,173 @@
+// lzbench_amd/csrc/zstdc_dfast_hip.hip -- zstd 1.5.2 frame compression at level 3 for gfx950 (LZH_CODEC_ZSTD_DFAST,
+// the hip_zstd_dfast row): the double-fast strategy, bit-exact with the reference build.  Level 3 is ZSTD_dfast in
+// all four source-size tables of clevels.h, so every chunk of a batch, the tail included, takes this path.
+//
+// A frame is processed block by block like the fast-strategy frames of zstdc_hip.hip, each block by two kernels:
+//
+//   lzh_zstd_dfast_match_kernel    one wave per frame: ZSTD_compressBlock_doubleFast_noDict_generic
+//                                  (zstd_double_fast.c:51-253) on the block; sequences + literals to the frame's
+//                                  scratch, the same FrameHdr contract as lzh_zstd_match_kernel.
+//   lzh_zstd_dfast_entropy_kernel  zstdc_entropy_body.inc with the level-3 window, block size and literal
+//                                  compression on: everything after the match finder is shared by fast and
+//                                  double-fast (strategy < ZSTD_lazy), so the body is the fast levels' as it is;
+//                                  the one strategy-dependent constant, ZSTD_selectEncodingType's 10 - strategy,
+//                                  is LZH_ZSTD_STRATEGY below.
+//
+// The match finder walks position by position (zstd_dfast_parse.h); the wave shares each position's loads,
+// counts match lengths 256 bytes a round and copies literals 64..256 bytes a round (count_fwd, count_bwd,
+// lit_copy of zstdc_hip.hip).  The two tables (long: 4 << hashLog, short: 4 << chainLog bytes, up to 768 KiB a
+// frame) live in the frame's scratch after the fast levels' areas and are served from L2; they start zeroed per
+// frame and persist across its blocks.  A table store becomes visible to the wave's later loads through a wait
+// for it (GlbTab::fence) and loads that bypass L1, as in the fast levels' scratch table.
+//
+// zstdc_hip.hip is included for its device functions alone (and compiled with its flags); nothing here changes
+// the fast levels' kernels.
+#define LZH_DEVICE_FUNCTIONS_ONLY 1
+#define LZH_ZSTD_STRATEGY 2   // ZSTD_dfast: ZSTD_selectEncodingType's thresholds (the one place the stage reads it)
+#include "zstdc_hip.hip"
+#include "zstd_dfast_parse.h"
+
+namespace zdf {
+
+// the level-3 parameters in the shape the entropy body reads (window, block size, literal compression on)
+__host__ __device__ inline zc::ZParams entropy_params(int level, uint64_t n) {
+    const DParams D = params_for(level, n);
+    zc::ZParams p{};
+    p.ok = D.ok;
+    p.wlog = D.wlog;
+    p.hlog = D.hlog;
+    p.mls = D.mls;
+    p.step = 2;
+    p.bsize = D.bsize;
+    p.lit_off = 0;                      // double-fast never disables literal compression
+    return p;
+}
+
+// dfast_block's environment on one wave: uniform loads of the frame, the two tables in the frame's scratch
+struct WaveEnv {
+    const Bytes& in;
+    zc::GlbTab L, S;
+    zc::SeqOut& O;
+    int lane;
+    __device__ __forceinline__ uint32_t r32(int pos) const { return uni(in.w32(max(pos, 0))); }
+    __device__ __forceinline__ uint64_t r64(int pos) const { return uni64(zc::ld64(in, max(pos, 0))); }
+    __device__ __forceinline__ int count_fwd(int a, int b, int maxn) const { return zc::count_fwd(in, a, b, maxn, lane); }
+    __device__ __forceinline__ int count_bwd(int a, int b, int maxn) const { return zc::count_bwd(in, a, b, maxn, lane); }
+    __device__ __forceinline__ uint32_t long_get(uint32_t h) const { return uni(L.get(h)); }
+    __device__ __forceinline__ uint32_t short_get(uint32_t h) const { return uni(S.get(h)); }
+    __device__ __forceinline__ void long_put(uint32_t h, uint32_t v) const { if (lane == 0) L.put(h, v); }
+    __device__ __forceinline__ void short_put(uint32_t h, uint32_t v) const { if (lane == 0) S.put(h, v); }
+    __device__ __forceinline__ void fence() const { L.fence(); }
+    __device__ __forceinline__ void seq(int from, int ll, uint32_t offBase, uint32_t mlen) const {
+        zc::lit_copy(in, from, O.lits, O.nl, ll, lane);
+        O.nl += ll;
+        O.put(lane, (uint32_t)ll, offBase, mlen);
+    }
+};
+
+}  // namespace zdf
+
+// one wave per frame; block k of every frame
+extern "C" __global__ void __launch_bounds__(64)
+lzh_zstd_dfast_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level,
+                            int k, uint8_t* scratch, uint64_t fstride, uint64_t seq_off, uint64_t lit_off,
+                            uint64_t tab_off) {
+    const int lane = threadIdx.x;
+    const uint64_t f = blockIdx.x;
+    const uint64_t ioff = f * chunk_size;
+    if (ioff >= n_total && !(n_total == 0 && f == 0)) return;
+    const uint64_t nf = n_total ? min(chunk_size, n_total - ioff) : 0;
+    const zdf::DParams P = zdf::params_for(level, nf);
+    if (!P.ok) return;
+    const uint64_t nblocks = nf ? (nf + P.bsize - 1) / P.bsize : 1;
+    if ((uint64_t)k >= nblocks) return;
+    uint8_t* fs = scratch + f * fstride;
+    rsrc_t hdr = make_rsrc(fs, 64);
+    const int bs = k * (int)P.bsize;
+    const int be = (int)min<uint64_t>(nf, (uint64_t)bs + P.bsize);
+    if (be - bs < 7) {                                   // ZSTD_buildSeqStore: too small, stored raw
+        if (lane == 0) { st_b32(hdr, 32, 1u); st_b32(hdr, 0, 0u); st_b32(hdr, 4, 0u); }
+        return;
+    }
+    Bytes in_b;
+    in_b.init(in + ioff, min<uint64_t>(in_readable - ioff, nf + 16));
+    SeqOut O;
+    O.seq = make_rsrc(fs + seq_off, (uint32_t)(lit_off - seq_off));
+    O.lits.init(fs + lit_off, P.bsize + 64);
+    O.ns = 0;
+    O.nl = 0;
+    uint32_t rep[2] = {1u, 4u};                          // repStartValue
+    if (k > 0) { rep[0] = uni(ld_b32(hdr, 16)); rep[1] = uni(ld_b32(hdr, 20)); }
+    const uint32_t lbytes = 4u << P.hlog, sbytes = 4u << P.clog;
+    zdf::WaveEnv E{in_b, GlbTab{make_rsrc(fs + tab_off, lbytes)}, GlbTab{make_rsrc(fs + tab_off + lbytes, sbytes)}, O, lane};
+    if (k == 0) {                                        // both tables start empty per frame
+        rsrc_t both = make_rsrc(fs + tab_off, lbytes + sbytes);
+        for (uint32_t i = lane; i < (lbytes + sbytes) / 4; i += 64) st_b32(both, (int)(i * 4), 0u);
+        E.fence();
+    }
+    const int anchor = zdf::dfast_block(E, P, bs, be, rep);
+    copy_span(in_b, anchor, O.lits, O.nl, be - anchor, lane, LZH_WAVE);   // last literals
+    O.nl += be - anchor;
+    if (lane == 0) {
+        st_b32(hdr, 0, (uint32_t)O.ns);
+        st_b32(hdr, 4, (uint32_t)O.nl);
+        st_b32(hdr, 8, rep[0]);
+        st_b32(hdr, 12, rep[1]);
+        st_b32(hdr, 32, 0u);
+    }
+}
+
+// one wave per frame; block k of every frame: the fast levels' entropy stage with the level-3 parameters
+extern "C" __global__ void __launch_bounds__(64)
+lzh_zstd_dfast_entropy_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level,
+                              int k, uint8_t* scratch, uint64_t fstride, uint64_t seq_off, uint64_t lit_off,
+                              uint64_t att_off, uint64_t tmp_off, uint8_t* stage, uint64_t stride, uint32_t* csizes) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds_raw[(sizeof(ze::Lds) + 3) / 4];
+    LDSA ze::Lds& L = *(LDSA ze::Lds*)lds_raw;
+    const int lane = threadIdx.x;
+    const uint64_t f = blockIdx.x;
+    const uint64_t ioff = f * chunk_size;
+    if (ioff >= n_total && !(n_total == 0 && f == 0)) return;
+    const uint64_t nf = n_total ? min(chunk_size, n_total - ioff) : 0;
+    // (the body asks params_for(level, nf) for the frame's parameters: here that name is the level-3 row)
+    const auto params_for = [](int lv, uint64_t n) { return zdf::entropy_params(lv, n); };
+#include "zstdc_entropy_body.inc"
+}
+
+#include <algorithm>
+#include "launch.h"
+
+size_t lzh_zstd_dfast_scratch_stride(size_t chunk_size) {
+    const zdf::DParams P = zdf::params_for(3, chunk_size);
+    // the tail chunk may use other tables (smaller chunks select other clevels rows): the largest of each
+    uint32_t hmax = P.hlog, cmax = P.clog;
+    for (int lg = 6; lg <= 31 && (1ull << (lg - 1)) < chunk_size; lg++) {
+        const zdf::DParams Q = zdf::params_for(3, std::min<uint64_t>(chunk_size, 1ull << lg));
+        hmax = std::max(hmax, Q.hlog);
+        cmax = std::max(cmax, Q.clog);
+    }
+    const zdf::DParams T = zdf::params_for(3, 1);
+    hmax = std::max(hmax, T.hlog);
+    cmax = std::max(cmax, T.clog);
+    const Layout Lo = layout_for(P.bsize, 16);   // offsets below tab_off do not depend on hlog
+    return (size_t)((Lo.tab_off + (4ull << hmax) + (4ull << cmax) + 255) & ~255ull);
+}
+
+hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
+                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                          uint8_t* scratch, hipStream_t s) {
+    if (nchunks == 0) return hipSuccess;
+    const zdf::DParams PF = zdf::params_for(level, chunk_size);
+    if (!PF.ok) return hipErrorInvalidValue;
+    const uint64_t fstride = lzh_zstd_dfast_scratch_stride(chunk_size);
+    const Layout Lo = layout_for(PF.bsize, 16);
+    const uint32_t nblocks = (uint32_t)((std::min<uint64_t>(chunk_size, std::max<uint64_t>(n_total, 1)) + PF.bsize - 1) / PF.bsize);
+    for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
+        hipLaunchKernelGGL(lzh_zstd_dfast_match_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable, chunk_size,
+                           level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off);
+        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable,
+                           chunk_size, level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off,
+                           stage, stride, csizes);
+    }
+    return hipGetLastError();
+}

@@ -624,6 +624,11 @@ lzh_zstd_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable,
 #endif
 
 // ======================================================================= entropy stage
+// The strategy number enters the entropy stage in one place, ZSTD_selectEncodingType's mult = 10 - strategy
+// (zstd_compress_sequences.c:182): ZSTD_fast here; zstdc_dfast_hip.hip compiles the stage for ZSTD_dfast (2).
+#ifndef LZH_ZSTD_STRATEGY
+#define LZH_ZSTD_STRATEGY 1
+#endif
 namespace ze {
 
 typedef int16_t s16;
@@ -1463,7 +1468,7 @@ __device__ int encode_sequences(LDSA Lds& L, const Bytes& att, const Bytes& tmp,
             else {
                 ty = 2;
                 if (defOk) {
-                    const uint32_t dynMin = ((1u << defLog[t]) * 9) >> 3;
+                    const uint32_t dynMin = ((1u << defLog[t]) * (10 - LZH_ZSTD_STRATEGY)) >> 3;
                     if ((uint32_t)ns < dynMin || big < ((uint32_t)ns >> (defLog[t] - 1))) ty = 0;
                 }
             }

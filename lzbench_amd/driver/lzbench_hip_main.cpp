@@ -103,6 +103,9 @@ static compressor_desc_t comp_desc[] = {
      lzbench_hip_deinit, lzbench_hip_compress_batch, lzbench_hip_decompress_batch},
     {"hip_zstd_fast", "1.5.2", -5, -1, 1, 0, lzbench_hip_zstd_compress, lzbench_hip_zstd_decompress,
      lzbench_hip_zstd_init, lzbench_hip_deinit, lzbench_hip_compress_batch, lzbench_hip_decompress_batch},
+    // zstd's default level, the double-fast strategy (LZH_CODEC_ZSTD_DFAST): -ehip_zstd_dfast,3
+    {"hip_zstd_dfast", "1.5.2", 3, 3, 1, 0, lzbench_hip_zstd_dfast_compress, lzbench_hip_zstd_decompress,
+     lzbench_hip_zstd_dfast_init, lzbench_hip_deinit, lzbench_hip_compress_batch, lzbench_hip_decompress_batch},
     // framed formats: an LZ4 frame per chunk (level = LZH_LZ4F_PARAMS: 4..7 = block size 64 KiB..4 MiB), and
     // the nvcomp_lz4 row's container (lzbench.h:218, levels 0..5 = chunks of 32 KiB << level)
     {"hip_lz4frame", "1.9.3", 4, 7, 1, 0, lzbench_hip_lz4frame_compress, lzbench_hip_lz4frame_decompress,
@@ -279,6 +282,7 @@ static void bench_one(params_t* P, std::vector<size_t>& file_sizes, const compre
     {   // GPU rows whose level the device codec does not cover for this chunk size (zstd level 2 is
         // double-fast above 256 KiB chunks): say so instead of an error row
         const int codec = d->init == lzbench_hip_zstd_init ? LZH_CODEC_ZSTD
+                        : d->init == lzbench_hip_zstd_dfast_init ? LZH_CODEC_ZSTD_DFAST
                         : d->init == lzbench_hip_lz4frame_init ? LZH_CODEC_LZ4F
                         : d->init == lzbench_hip_nvcomp_lz4_init ? LZH_CODEC_NVLZ4 : -1;
         if (codec >= 0 && !lzh_level_supported(codec, level, chunk)) {
