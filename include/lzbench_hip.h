@@ -406,6 +406,71 @@ int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, 
                                          size_t max_chunk_bytes, int32_t* d_status, void* d_temp, size_t temp_bytes,
                                          void* hip_stream);
 
+/* ---- 3e. ragged zstd level-3 batches (the double-fast strategy) ------------------------- */
+/* lzh_zstd_compress_ragged_async and lzh_zstd_compress_ragged_compact_async for zstd level 3 (LZH_CODEC_ZSTD_DFAST
+ * above), under names of their own: the calls of 3b keep refusing the codec and those of 3c the level.  The contract
+ * is that of 3c, word for word -- device arrays of nchunks entries, chunk i the d_in_bytes[i] bytes at d_in_ptrs[i],
+ * any alignment, chunks may overlap or repeat; 16 readable bytes after every input chunk; max_chunk_bytes at most
+ * 16 MiB, else LZH_EARG; nchunks == 0 returns LZH_OK and launches nothing; a chunk whose device-side size is larger
+ * than max_chunk_bytes is not processed and no kernel touches its slots (d_csizes[i] = 0, no packed bytes);
+ * packed_cap is enforced on the device by the pack kernel and d_offsets[nchunks] > packed_cap reports an incomplete
+ * output; a chunk whose compressed size equals its size is stored raw; the order of the checks (level /
+ * max_chunk_bytes, nchunks == 0: LZH_OK, null pointers, then temp_bytes below the sizing answer: LZH_ESPACE), all
+ * before any device call; every launch on hip_stream, no side stream, event, host synchronisation or size read
+ * back, so a captured call has no parallel branches -- with these exceptions:
+ *   level must be 3: any other level returns LZH_EARG, and the two sizing functions return 0 for it (as they do
+ *       for max_chunk_bytes above 16 MiB);
+ *   frame i is the bytes lzh_compress_async(LZH_CODEC_ZSTD_DFAST, 3, ..., n = size, chunk_size >= size) writes --
+ *       ZSTD_getParams(3, size, 0), content size, no checksum; equal sizes over contiguous input give the uniform
+ *       call's d_csizes, d_offsets and packed bytes.  A zero-length chunk is legal: the 9-byte frame.
+ * Uniform-slot temp: nchunks x (lzh_stage_stride(LZH_CODEC_ZSTD, max_chunk_bytes) + the level-3 scratch stride of
+ * max_chunk_bytes), exactly (no spare bytes; so 0 for nchunks == 0, where the call launches nothing and needs no
+ * temp), a batch of empty chunks laid out as one of 1-byte chunks.  The scratch stride is the
+ * areas of 3c (about 8 x min(max_chunk_bytes, 128 KiB) + 6.5 KiB) and the two double-fast tables, the long one of
+ * 4 << hashLog and the short one of 4 << chainLog bytes, each the largest of any size up to max_chunk_bytes (768 KiB
+ * above 256 KiB chunks): 1,447,680 bytes at 128 KiB (1.51 MiB a chunk with the staging slot), 350,208 a chunk at
+ * 16 KiB.
+ * Compact temp (lzh_zstd_dfast_compress_ragged_compact_async): every chunk's staging slot and scratch slot sized from
+ * that chunk's own d_in_bytes[i] (256-aligned) and placed by an exclusive scan on the device, the promise of
+ * total_in_bytes, the rule for a chunk whose slots end outside their regions (d_csizes[i] = 0, nothing touched) and
+ * the descriptor bounds as in 3c.  A chunk of n bytes takes a staging slot of lzh_stage_stride(LZH_CODEC_ZSTD, n) and
+ * a scratch slot of the areas for its own block size plus its own two tables (ZSTD_getParams(3, n, 0): under 24 x n
+ * from 64 bytes on, 768 bytes below; 48 KiB for a chunk of 4 KiB); an empty chunk takes the slots of a 1-byte chunk.
+ * The scratch region is the smaller of nchunks x the uniform-slot scratch stride and the sum of three bounds:
+ * min(8 x total_in_bytes, nchunks x 8 x min(max_chunk_bytes, 128 KiB)), 6656 bytes a chunk, and the tables,
+ * min(24 x total_in_bytes + 768 x nchunks, nchunks x the largest two tables up to max_chunk_bytes); the staging
+ * region as in 3c.  The answer covers every batch of at most nchunks chunks, each of at most max_chunk_bytes, that
+ * sums to at most total_in_bytes; it is non-decreasing in each of the three and never above
+ * lzh_zstd_dfast_ragged_compress_temp_bytes(3, max_chunk_bytes, nchunks) plus the four per-chunk arrays (two u32 of
+ * nchunks, two u64 of nchunks + 1, each 256-aligned).  The sizing function's own answers, next to 3c's:
+ *   4096 chunks, one of 16 MiB and 4095 of 4 KiB (33,550,336 bytes in all):   1,139,171,840 bytes (1.06 GiB; level 1
+ *       in 3c: 867,689,472), where lzh_zstd_dfast_ragged_compress_temp_bytes answers 76,529,270,784 (71.27 GiB);
+ *   4096 chunks of 128 KiB:   6,469,812,736 bytes (6.03 GiB) against 6,469,713,920 -- a uniform batch gains nothing
+ *       (the same slots and the four arrays, 98,816 bytes).
+ * Decoding: no call of its own.  These are LZH_CODEC_ZSTD's frames and decode with lzh_zstd_decompress_ragged_async,
+ * in the one-wave or the four-kernel split decoder by that call's temp_bytes
+ * (lzh_zstd_ragged_decompress_temp_bytes / lzh_zstd_ragged_decompress_split_temp_bytes);
+ * lzh_zstd_ragged_max_packed_bytes bounds the packed output (the frames have LZH_CODEC_ZSTD's bound).
+ * The two debug calls are those of 3c for this layout (host arithmetic only; LZH_EARG where the async call would
+ * return it, or for a null pointer): the host mirror of the slot placement, and the two regions as byte ranges of
+ * d_temp, out[0], out[1] = offset and size of the staging region, out[2], out[3] = of the scratch region. */
+size_t lzh_zstd_dfast_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks);
+int lzh_zstd_dfast_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                         size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                                         uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                                         void* hip_stream);
+size_t lzh_zstd_dfast_ragged_compact_compress_temp_bytes(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                         size_t nchunks);
+int lzh_zstd_dfast_compress_ragged_compact_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                                 size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
+                                                 void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                                 uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream);
+int lzh_debug_zstd_dfast_ragged_compact_slots(int level, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                              size_t total_in_bytes, uint64_t* stage_off, uint64_t* scratch_off,
+                                              uint8_t* processed);
+int lzh_debug_zstd_dfast_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                size_t nchunks, uint64_t* out);
+
 /* Debug only, host arithmetic only (they may change; no decode call takes this layout yet, so the split decoder runs
  * with the uniform-slot temp above alone and there is no public sizing function): a compact layout of the split
  * decoder's temp, in which every frame's area is laid out for that frame's own decoded size and placed by an

@@ -116,6 +116,12 @@ SIGNATURES = {
     "lzh_zstd_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
+    "lzh_zstd_dfast_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
+    "lzh_zstd_dfast_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_zstd_dfast_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
+    "lzh_zstd_dfast_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_debug_zstd_dfast_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    "lzh_debug_zstd_dfast_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
     "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
     "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
@@ -415,6 +421,10 @@ class RaggedCodec:
     small arrays, the output is the same, and a batch must keep its total within max_total_bytes
     as with compact=True.  compact=True itself raises ValueError for zstd (the LZ4 / snappy calls refuse the
     codec): compact_scratch is the zstd option.
+    zstd_dfast (level 3, the double-fast strategy; any other level: ValueError) is zstd in everything above -- the
+    frames, compact_scratch (at most 33 x max_total_bytes plus 7.5 KiB per chunk: a frame keeps two tables), the
+    refusal of compact=True and of a dictionary, the decoder and split_decode below -- through the compress calls
+    of include/lzbench_hip.h 3e.
     split_decode=True (zstd only, else ValueError) sizes the decompress temp for the four-kernel split decoder
     (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
     batches); where there is none (max_chunk_bytes below 16 KiB) the temp stays the small one and every frame
@@ -438,7 +448,9 @@ class RaggedCodec:
         self.max_total = max_chunks * max_chunk_bytes if max_total_bytes is None else max_total_bytes
         L = lib()
         self.compact = compact
-        self.zstd = self.codec == LZH_CODEC_ZSTD
+        # (zstd_dfast, level 3: the frames, the decoder, the options and the refusals of zstd; 3e's compress calls)
+        dfast = self.codec == LZH_CODEC_ZSTD_DFAST
+        self.zstd = self.codec == LZH_CODEC_ZSTD or dfast
         if self.zstd and compact:
             raise ValueError("ragged batches: compact=True is the LZ4 / snappy layout; for zstd pass compact_scratch=True")
         if compact_scratch and not self.zstd:
@@ -456,8 +468,14 @@ class RaggedCodec:
         # a caller may lower its promise between calls)
         self._promise = compact or compact_scratch
         if self.zstd:
-            self._compress = L.lzh_zstd_compress_ragged_compact_async if compact_scratch else L.lzh_zstd_compress_ragged_async
-            sizing = L.lzh_zstd_ragged_compact_compress_temp_bytes if compact_scratch else L.lzh_zstd_ragged_compress_temp_bytes
+            if dfast:
+                self._compress = (L.lzh_zstd_dfast_compress_ragged_compact_async if compact_scratch
+                                  else L.lzh_zstd_dfast_compress_ragged_async)
+                sizing = (L.lzh_zstd_dfast_ragged_compact_compress_temp_bytes if compact_scratch
+                          else L.lzh_zstd_dfast_ragged_compress_temp_bytes)
+            else:
+                self._compress = L.lzh_zstd_compress_ragged_compact_async if compact_scratch else L.lzh_zstd_compress_ragged_async
+                sizing = L.lzh_zstd_ragged_compact_compress_temp_bytes if compact_scratch else L.lzh_zstd_ragged_compress_temp_bytes
             self._chead, self._decompress, self._dhead = (self.level,), L.lzh_zstd_decompress_ragged_async, ()
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
             if split_decode:   # (0: no split decoder for chunks of this size)

@@ -348,7 +348,7 @@ size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchu
 
 }  // extern "C"
 
-// The four ragged compress calls (3b, 3c; uniform slots, compact layout): the argument checks in their order (ok: the
+// The ragged compress calls (3b, 3c, 3d, 3e; uniform slots, compact layout): the argument checks in their order (ok: the
 // codec / level takes max_chunk_bytes; grid_factor: launch blocks per chunk; temp_need: the layout's total), then
 // compress() -> scan -> pack(), the two callables enqueueing on s and returning HIP's verdict.
 template <class Compress, class Pack>
@@ -739,6 +739,83 @@ int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_pt
         [&] {
             return lzh_launch_zstd_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes, k,
                                            base + t.recs, t.layout(base), s);
+        },
+        [&] {
+            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
+                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
+        });
+}
+
+// ---- 3e. ragged zstd level-3 batches (the double-fast strategy): entry points of their own -- the calls of 3b keep
+// refusing the codec and those of 3c the level -- through the skeleton of 3c; zstd_dfast_ragged_temp and
+// zstd_dfast_compact_temp lay the temp out for the sizing calls, the async calls and the debug calls.  The frames
+// decode with lzh_zstd_decompress_ragged_async ----
+static bool zstd_dfast_ragged_ok(int level, size_t max_chunk_bytes) {
+    return level == 3 && max_chunk_bytes <= kLz4SplitMax;
+}
+
+size_t lzh_zstd_dfast_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_dfast_ragged_ok(level, max_chunk_bytes) ? zstd_dfast_ragged_temp(nchunks, max_chunk_bytes).total : 0;
+}
+
+int lzh_zstd_dfast_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                         size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                                         uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                                         void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const ChunkTemp t = zstd_dfast_ragged_temp(nchunks, max_chunk_bytes);
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    return ragged_compress(
+        zstd_dfast_ragged_ok(level, max_chunk_bytes), nchunks,
+        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
+        d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_dfast_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride,
+                                                d_csizes, k, base + t.recs, t.rec_stride, s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
+}
+
+size_t lzh_zstd_dfast_ragged_compact_compress_temp_bytes(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                         size_t nchunks) {
+    if (!zstd_dfast_ragged_ok(level, max_chunk_bytes)) return 0;
+    return zstd_dfast_compact_temp(total_in_bytes, max_chunk_bytes, nchunks).total;
+}
+
+int lzh_debug_zstd_dfast_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes,
+                                                size_t nchunks, uint64_t* out) {
+    return compact_regions_out(zstd_dfast_ragged_ok(level, max_chunk_bytes),
+                               zstd_dfast_compact_temp(total_in_bytes, max_chunk_bytes, nchunks), out);
+}
+
+int lzh_debug_zstd_dfast_ragged_compact_slots(int level, const uint64_t* sizes, size_t nchunks, size_t max_chunk_bytes,
+                                              size_t total_in_bytes, uint64_t* stage_off, uint64_t* scratch_off,
+                                              uint8_t* processed) {
+    return compact_slots_mirror(zstd_dfast_ragged_ok(level, max_chunk_bytes),
+                                lzh_zstd_dfast_compact_regions(total_in_bytes, max_chunk_bytes, nchunks), sizes, nchunks,
+                                max_chunk_bytes, stage_off, scratch_off, processed,
+                                [&](uint64_t n) { return lzh_zstd_dfast_compact_slot(n); });
+}
+
+int lzh_zstd_dfast_compress_ragged_compact_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                                 size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
+                                                 void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                                 uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const CompactTemp t = zstd_dfast_compact_temp(total_in_bytes, max_chunk_bytes, nchunks);
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    return ragged_compress(
+        zstd_dfast_ragged_ok(level, max_chunk_bytes), nchunks,
+        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
+        d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_dfast_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes,
+                                                 k, base + t.recs, t.layout(base), s);
         },
         [&] {
             return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,

@@ -197,6 +197,23 @@ hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* i
                                    uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
                                    const LzhCompactLayout& L, hipStream_t s);
 
+// ragged zstd level-3 batches (zstd_dfast_ragged_hip.hip, zstd_dfast_slots.h; include/lzbench_hip.h 3e): the
+// launchers of the two layouts above for the double-fast strategy.  lzh_launch_zstd_dfast_ragged: staging slots of
+// `stride` and scratch areas of `fstride` (at least lzh_zstd_dfast_scratch_stride(max(max_bytes, 1))), slot i for
+// chunk i.  lzh_launch_zstd_dfast_compact: the compact layout struct with the record fields carrying the scratch
+// slots; it fills the four arrays (the level-3 slot-size kernel, then lzh_launch_compact_scans).  Both run one match /
+// entropy pair per block index, ceil(max(max_bytes, 1) / block size) of them, every launch on s; level must be 3.
+// A chunk larger than max_bytes, or (compact) one with a slot that ends past its region, gets csizes[i] = 0.  The two
+// host functions are the slot arithmetic as {staging bytes, scratch bytes}: the two regions, a chunk's two slots.
+hipError_t lzh_launch_zstd_dfast_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                        int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                        uint8_t* scratch, uint64_t fstride, hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                         int level, uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
+                                         const LzhCompactLayout& L, hipStream_t s);
+LzhCompactRegions lzh_zstd_dfast_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks);
+LzhCompactRegions lzh_zstd_dfast_compact_slot(uint64_t n);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

@@ -78,6 +78,12 @@ struct CompactSlot {
     __device__ __forceinline__ explicit operator uint64_t() const { return bytes; }
 };
 __device__ __forceinline__ uint64_t operator*(uint64_t, CompactSlot s) { return s.off; }
+// The zstd bodies (zstd_ragged_compact_hip.hip, zstd_dfast_ragged_hip.hip) pass a slot where they mean its size,
+// `out.init(stage + f * stride, stride)`: the conversion that the LZ4 / snappy bodies must spell as a cast is
+// implicit for them
+struct ZstdSlot : CompactSlot {
+    __device__ __forceinline__ operator uint64_t() const { return bytes; }
+};
 
 // Chunk i of a compact batch: ragged_span's pointer and size and the chunk's two slots, loaded once and
 // wave-uniform.  false = not processed (over max_bytes, or a slot that ends past its region).

@@ -163,6 +163,32 @@ static inline CompactTemp zstd_compact_temp(int level, size_t total_in, size_t m
     return t;
 }
 
+// ---- ragged zstd level-3 compression (3e), both layouts without spare bytes, so the published formulas are exact:
+// uniform slots: k staging slots of lzh_stage_stride(LZH_CODEC_ZSTD, chunk) | k scratch areas of the level-3 stride
+// (a batch of empty chunks is laid out as one of 1-byte chunks, as in 3c);
+// compact: staging region | scratch region (zstd_dfast_slots.h) | the placement's four arrays -- each region at most
+// k x the slot above, so the total never passes the uniform-slot one by more than the four arrays.
+static inline ChunkTemp zstd_dfast_ragged_temp(size_t k, size_t chunk) {
+    ChunkTemp t = {};
+    TempCursor c;
+    chunk = std::max<size_t>(chunk, 1);
+    t.stride = lzh_stage_stride(LZH_CODEC_ZSTD, chunk);
+    t.rec_stride = zstd_dfast_scratch_stride(chunk);
+    t.stage = c.take(k * t.stride);
+    t.recs = t.hdr = c.take(k * t.rec_stride);
+    t.total = c.at;
+    return t;
+}
+static inline CompactTemp zstd_dfast_compact_temp(size_t total_in, size_t max_bytes, size_t nchunks) {
+    CompactTemp t = {};   // (no record counts: hdr stays 0)
+    TempCursor c;
+    t.reg = lzh_zstd_dfast_compact_regions(total_in, max_bytes, nchunks);
+    t.stage = c.take(t.reg.stage);
+    t.recs = c.take(t.reg.recs);
+    compact_arrays(t, c, nchunks, 0);
+    return t;
+}
+
 // ---- decompression: the scanned offsets (k + 1 u64, used when the caller passes none), then
 //   frames: maxbpf block descriptors per frame (32 bytes each) | block statuses | frame statuses
 //   zstd, snappy: the temp of the split decoder (decode_hip.hip carves it), where there is one

@@ -16,9 +16,9 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define LZH_HD __host__ __device__
+#define ZDF_HD __host__ __device__
 #else
-#define LZH_HD
+#define ZDF_HD
 #endif
 
 namespace zdf {
@@ -30,7 +30,7 @@ struct DParams {
 
 // ZSTD_getParams(3, n, 0) after ZSTD_adjustCParams_internal (zstd_compress.c:1316-1373); clevels.h:25-111 level 3
 // is {W, C, H, S, minMatch, 0, ZSTD_dfast} in all four tables.  n == 0: unknown size, table 0 unadjusted.
-LZH_HD inline DParams params_for(int level, uint64_t n) {
+ZDF_HD inline DParams params_for(int level, uint64_t n) {
     const uint8_t rows[4][4] = {{21, 16, 17, 5}, {18, 16, 16, 4}, {17, 15, 16, 5}, {14, 14, 15, 4}};
     DParams p{};
     if (level != 3) return p;
@@ -58,15 +58,15 @@ LZH_HD inline DParams params_for(int level, uint64_t n) {
     return p;
 }
 
-LZH_HD inline uint32_t hash8(uint64_t v, uint32_t hlog) { return (uint32_t)((v * 0xCF1BBCDCB7A56463ull) >> (64 - hlog)); }
-LZH_HD inline uint32_t hash_short(uint64_t v, uint32_t hlog, uint32_t mls) {
+ZDF_HD inline uint32_t hash8(uint64_t v, uint32_t hlog) { return (uint32_t)((v * 0xCF1BBCDCB7A56463ull) >> (64 - hlog)); }
+ZDF_HD inline uint32_t hash_short(uint64_t v, uint32_t hlog, uint32_t mls) {
     return mls == 5 ? (uint32_t)(((v << 24) * 889523592379ull) >> (64 - hlog)) : ((uint32_t)v * 2654435761u) >> (32 - hlog);
 }
 
 // The parse of block [bs, be) of a frame; rep: the repcodes, in and out.  The literals after the last sequence
 // ([return value, be)) are the caller's to store.
 template <class Env>
-LZH_HD int dfast_block(Env& E, const DParams& P, int bs, int be, uint32_t rep[2]) {
+ZDF_HD int dfast_block(Env& E, const DParams& P, int bs, int be, uint32_t rep[2]) {
     const int W = 1 << P.wlog;
     const int dl = bs > W ? bs - W : 0;                       // ZSTD_window_enforceMaxDist at the block start
     const int plow = (be - dl > W) ? be - W : dl;            // ZSTD_getLowestPrefixIndex(endIndex)

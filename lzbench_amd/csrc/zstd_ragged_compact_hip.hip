@@ -27,12 +27,7 @@
 #include "zstdc_hip.hip"
 #include "zstd_ragged_slots.h"
 
-// (the bodies pass a slot where they mean its size, `out.init(stage + f * stride, stride)`: the conversion that the
-// LZ4 / snappy bodies must spell as a cast is implicit here)
-struct ZstdSlot : CompactSlot {
-    __device__ __forceinline__ operator uint64_t() const { return bytes; }
-};
-
+// (ZstdSlot: ragged_slots.h)
 // -------------------------------------------------------------------------------------- slot sizes
 extern "C" __global__ void __launch_bounds__(256)
 lzh_zstd_compact_slots_kernel(const uint64_t* in_bytes, uint64_t max_bytes, int level, uint32_t* stage_sz,

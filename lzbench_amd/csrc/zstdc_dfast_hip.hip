@@ -67,6 +67,7 @@ struct WaveEnv {
 
 }  // namespace zdf
 
+#ifndef LZH_DFAST_DEVICE_FUNCTIONS_ONLY   // (zstd_dfast_ragged_hip.hip includes this file for the above and the kernel bodies alone)
 // one wave per frame; block k of every frame
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_dfast_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level,
@@ -77,44 +78,7 @@ lzh_zstd_dfast_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_rea
     const uint64_t ioff = f * chunk_size;
     if (ioff >= n_total && !(n_total == 0 && f == 0)) return;
     const uint64_t nf = n_total ? min(chunk_size, n_total - ioff) : 0;
-    const zdf::DParams P = zdf::params_for(level, nf);
-    if (!P.ok) return;
-    const uint64_t nblocks = nf ? (nf + P.bsize - 1) / P.bsize : 1;
-    if ((uint64_t)k >= nblocks) return;
-    uint8_t* fs = scratch + f * fstride;
-    rsrc_t hdr = make_rsrc(fs, 64);
-    const int bs = k * (int)P.bsize;
-    const int be = (int)min<uint64_t>(nf, (uint64_t)bs + P.bsize);
-    if (be - bs < 7) {                                   // ZSTD_buildSeqStore: too small, stored raw
-        if (lane == 0) { st_b32(hdr, 32, 1u); st_b32(hdr, 0, 0u); st_b32(hdr, 4, 0u); }
-        return;
-    }
-    Bytes in_b;
-    in_b.init(in + ioff, min<uint64_t>(in_readable - ioff, nf + 16));
-    SeqOut O;
-    O.seq = make_rsrc(fs + seq_off, (uint32_t)(lit_off - seq_off));
-    O.lits.init(fs + lit_off, P.bsize + 64);
-    O.ns = 0;
-    O.nl = 0;
-    uint32_t rep[2] = {1u, 4u};                          // repStartValue
-    if (k > 0) { rep[0] = uni(ld_b32(hdr, 16)); rep[1] = uni(ld_b32(hdr, 20)); }
-    const uint32_t lbytes = 4u << P.hlog, sbytes = 4u << P.clog;
-    zdf::WaveEnv E{in_b, GlbTab{make_rsrc(fs + tab_off, lbytes)}, GlbTab{make_rsrc(fs + tab_off + lbytes, sbytes)}, O, lane};
-    if (k == 0) {                                        // both tables start empty per frame
-        rsrc_t both = make_rsrc(fs + tab_off, lbytes + sbytes);
-        for (uint32_t i = lane; i < (lbytes + sbytes) / 4; i += 64) st_b32(both, (int)(i * 4), 0u);
-        E.fence();
-    }
-    const int anchor = zdf::dfast_block(E, P, bs, be, rep);
-    copy_span(in_b, anchor, O.lits, O.nl, be - anchor, lane, LZH_WAVE);   // last literals
-    O.nl += be - anchor;
-    if (lane == 0) {
-        st_b32(hdr, 0, (uint32_t)O.ns);
-        st_b32(hdr, 4, (uint32_t)O.nl);
-        st_b32(hdr, 8, rep[0]);
-        st_b32(hdr, 12, rep[1]);
-        st_b32(hdr, 32, 0u);
-    }
+#include "zstdc_dfast_match_body.inc"
 }
 
 // one wave per frame; block k of every frame: the fast levels' entropy stage with the level-3 parameters
@@ -171,3 +135,4 @@ hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, u
     }
     return hipGetLastError();
 }
+#endif   // LZH_DFAST_DEVICE_FUNCTIONS_ONLY
