@@ -78,6 +78,26 @@ int64_t ref_zstd_decompress(const char* in, size_t csize, char* out, size_t cap)
     return ZSTD_isError(r) ? -1 : (int64_t)r;
 }
 int ref_zstd_version(void) { return (int)ZSTD_versionNumber(); }
+/* the reference's own parse of a frame: ZSTD_generateSequences (static-linking-only API) at that level on a fresh
+ * context.  out: 4 words per ZSTD_Sequence (offset, litLength, matchLength, rep); a block ends with an entry of
+ * offset 0 and matchLength 0 whose litLength is the block's last literals.  Returns the entries, -1 on error.
+ * In this mode the library confirms the repcodes after every block it searches and collects nothing for a block too
+ * small to search (zstd_compress.c ZSTD_compressBlock_internal), so the parse is a real compression's only for
+ * frames of compressed blocks alone. */
+int64_t ref_zstd_generate_sequences(const char* in, size_t n, int level, uint32_t* out, size_t cap) {
+    static_assert(sizeof(ZSTD_Sequence) == 16, "ZSTD_Sequence is four 32-bit words");
+    ZSTD_CCtx* c = ZSTD_createCCtx();
+    if (!c) return -1;
+    ZSTD_CCtx_setParameter(c, ZSTD_c_compressionLevel, level);
+    std::vector<ZSTD_Sequence> s(cap);
+    const size_t r = ZSTD_generateSequences(c, s.data(), cap, in, n);
+    ZSTD_freeCCtx(c);
+    if (ZSTD_isError(r) || r > cap) return -1;
+    for (size_t i = 0; i < r; i++) {
+        out[4 * i] = s[i].offset; out[4 * i + 1] = s[i].litLength; out[4 * i + 2] = s[i].matchLength; out[4 * i + 3] = s[i].rep;
+    }
+    return (int64_t)r;
+}
 
 /* params as oracle_lz4f_compress: bits 0-2 blockSizeID (0 default), 0x10 block checksum, 0x20 content
  * checksum, 0x40 content size, 0x80 linked blocks (LZ4F_blockLinked, the LZ4F default), bits 8-15
