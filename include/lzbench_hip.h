@@ -471,6 +471,67 @@ int lzh_debug_zstd_dfast_ragged_compact_slots(int level, const uint64_t* sizes, 
 int lzh_debug_zstd_dfast_ragged_compact_regions(int level, size_t total_in_bytes, size_t max_chunk_bytes,
                                                 size_t nchunks, uint64_t* out);
 
+/* ---- 3f. ragged zstd batches with a shared dictionary ------------------------------------- */
+/* lzh_zstd_compress_ragged_async / lzh_zstd_decompress_ragged_async with one raw-content dictionary shared by every
+ * chunk of the batch: what ZSTD_compress_usingDict and ZSTD_decompress_usingDict do for small records (pages, log
+ * lines, column chunks), which alone find little to match -- 1,000 bytes of word text: 566 bytes alone, 379 with a
+ * 4 KiB dictionary of the same vocabulary (level 1).  The contract is that of 3c, word for word -- device arrays of
+ * nchunks entries, any alignment, chunks may overlap or repeat; 16 readable bytes after every input chunk; nchunks == 0
+ * returns LZH_OK and launches nothing; a chunk whose device-side size is larger than max_chunk_bytes is not processed
+ * and no kernel touches a slot for it (d_csizes[i] = 0 / d_status[i] = -1); packed_cap enforced on the device by the
+ * pack kernel; d_offsets of the decompress call may be NULL; the raw-store rule on both sides; the packed layout, the
+ * scan and the pack of lzh_zstd_compress_ragged_async; every launch on hip_stream, no side stream, event, host
+ * synchronisation or size read back -- but for the dictionary arguments and the limits:
+ *   d_dict, dict_bytes: the dictionary, one device buffer of any alignment with 16 readable bytes after it;
+ *       8 <= dict_bytes <= 131072, else LZH_EARG (below 8 bytes the reference loads nothing; 131072 covers zstd's
+ *       default trained size of 112,640 bytes).  The bytes are always used as content: a buffer that begins with
+ *       zstd's dictionary magic (37 A4 30 EC) would be parsed by the reference as a trained dictionary with entropy
+ *       tables, and this call does not do that -- trained dictionaries are out of scope;
+ *   max_chunk_bytes <= 131072, else LZH_EARG: dictionary plus chunk never pass 256 KiB, every frame has one block
+ *       inside its window and the dictionary is never invalidated mid-frame;
+ *   level: 1 and -1 .. -5, the levels whose row is ZSTD_fast in all four tables, else LZH_EARG (levels 2 and 3:
+ *       double-fast with a dictionary is not built).
+ * The sizing functions return 0 exactly where the calls return LZH_EARG for those arguments; they are host arithmetic
+ * and non-decreasing in dict_bytes, max_chunk_bytes and nchunks (and the same for every accepted level).  Check order:
+ * arguments, nchunks == 0, null pointers (d_dict among them), then temp_bytes below the sizing answer: LZH_ESPACE; all
+ * before any device call.
+ * Compressed bytes: frame i is exactly what zstd 1.5.2 writes for ZSTD_compress_usingDict(cctx, dst, cap, chunk, n,
+ * dict, dict_bytes, level) on a fresh ZSTD_CCtx when the dictionary lies in a buffer of its own, not directly before
+ * the chunk (adjacent, the reference runs its prefix parser and the bytes differ from about 300-byte chunks on):
+ * ZSTD_getParams_internal(level, n, dict_bytes) -- the row by n + dict_bytes, the window cut to ceil log2 of it --
+ * ZSTD_loadDictionaryContent's table fill, ZSTD_compressBlock_fast_extDict_generic, and the frame of 3c (content
+ * size, no checksum, dictionary id 0 and so no id field, single segment).  A chunk under 7 bytes gives the bytes of
+ * the plain call, an empty one the 9-byte frame.
+ * Decoding: d_status[i] and the bytes are those of ZSTD_decompress_usingDict(dctx, dst, d_out_bytes[i], src, csize,
+ * dict, dict_bytes) for any frame of lzbench's shape, also one no encoder here writes (the reference at levels 3, 5,
+ * 19 with the dictionary): an offset may reach dict_bytes before the chunk's first byte, one more gives -1; a match
+ * may start in the dictionary and run on into the output; frames written without a dictionary decode as before; a
+ * frame with a dictionary id field reports -2.  The one-wave decoder only: no split temp is accepted.
+ * Temp: nchunks staging slots of lzh_stage_stride(LZH_CODEC_ZSTD, max_chunk_bytes), nchunks scratch areas (the areas
+ * of 3c for a block of max_chunk_bytes and the frame's own copy of the dictionary's table: 4 << hashLog bytes, the
+ * largest any frame of such a batch can take, 128 KiB once dictionary plus chunk pass 8 KiB), and one filled table per
+ * (hashLog, minMatch) class a batch can take, built once per call (a constant 359,936 bytes); the scanned offsets for
+ * decompression.
+ * The two debug calls are host arithmetic only: lzh_debug_zstd_dict_params writes windowLog, hashLog, minMatch,
+ * targetLength and the block size of ZSTD_getParams(level, n, dict_bytes) to out[0 .. 5); lzh_debug_zstd_dict_parse
+ * walks the parse on the host (host pointers, 16 readable bytes after each) and writes the first cap sequences as
+ * (literal length, match length, offBase) triples, returning the count; LZH_EARG where the async call would return it
+ * (n taking max_chunk_bytes' place) or for a null pointer. */
+size_t lzh_zstd_dict_compress_temp_bytes(int level, size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_zstd_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks);
+int lzh_zstd_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes,
+                                        const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                        size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                        uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream);
+int lzh_zstd_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
+                                          size_t packed_readable, const uint32_t* d_csizes, const uint64_t* d_offsets,
+                                          void* const* d_out_ptrs, const uint64_t* d_out_bytes, size_t nchunks,
+                                          size_t max_chunk_bytes, int32_t* d_status, void* d_temp, size_t temp_bytes,
+                                          void* hip_stream);
+int lzh_debug_zstd_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out);
+long lzh_debug_zstd_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
+                               uint32_t* seqs, size_t cap);
+
 /* Debug only, host arithmetic only (they may change; no decode call takes this layout yet, so the split decoder runs
  * with the uniform-slot temp above alone and there is no public sizing function): a compact layout of the split
  * decoder's temp, in which every frame's area is laid out for that frame's own decoded size and placed by an

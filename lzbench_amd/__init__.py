@@ -130,6 +130,12 @@ SIGNATURES = {
     "lzh_lz4_dict_decompress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
     "lzh_lz4_compress_ragged_dict_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_lz4_decompress_ragged_dict_async": (C.c_int, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_zstd_dict_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
+    "lzh_zstd_dict_decompress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "lzh_zstd_compress_ragged_dict_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "lzh_zstd_decompress_ragged_dict_async": (C.c_int, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_debug_zstd_dict_params": (C.c_int, [C.c_int, _SZ, _SZ, _P]),
+    "lzh_debug_zstd_dict_parse": (C.c_long, [C.c_int, _P, _SZ, _P, _SZ, _P, _SZ]),
     "lzh_compress_kernel_only": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_kernel_stage": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
@@ -423,7 +429,7 @@ class RaggedCodec:
     codec): compact_scratch is the zstd option.
     zstd_dfast (level 3, the double-fast strategy; any other level: ValueError) is zstd in everything above -- the
     frames, compact_scratch (at most 33 x max_total_bytes plus 7.5 KiB per chunk: a frame keeps two tables), the
-    refusal of compact=True and of a dictionary, the decoder and split_decode below -- through the compress calls
+    refusal of compact=True, the refusal of a dictionary (zstd_dfast has none), the decoder and split_decode below -- through the compress calls
     of include/lzbench_hip.h 3e.
     split_decode=True (zstd only, else ValueError) sizes the decompress temp for the four-kernel split decoder
     (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
@@ -434,6 +440,11 @@ class RaggedCodec:
     LZ4_loadDict + LZ4_compress_fast_continue write for each chunk, decompress() is LZ4_decompress_safe_usingDict.
     The tensor is copied once (self.dictionary); small records that share content with it compress several times
     smaller than alone.
+    With zstd / zstd_fast the dictionary (8 .. 131072 bytes, raw content; chunks up to 128 KiB; levels 1 and
+    -1 .. -5; no compact_scratch, no split_decode, else ValueError) goes through include/lzbench_hip.h 3f: compress()
+    writes what ZSTD_compress_usingDict writes for each chunk with the dictionary in a buffer of its own, decompress()
+    is ZSTD_decompress_usingDict.  A tensor that begins with zstd's dictionary magic (37 A4 30 EC) is refused with
+    ValueError: the reference would read it as a trained dictionary, these calls use the bytes as content.
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
@@ -459,15 +470,36 @@ class RaggedCodec:
         if split_decode and not self.zstd:
             raise ValueError("ragged batches: split_decode is a zstd option")
         self.split_decode = split_decode
-        if dictionary is not None and (codec != "lz4" and codec != "lz4fast" or compact):
-            raise ValueError("ragged batches: a dictionary goes with codec lz4 / lz4fast and the uniform-slot layout "
-                             "(compact=False)")
+        zdict = dictionary is not None and codec in ("zstd", "zstd_fast")
+        if zdict and (compact_scratch or split_decode):
+            raise ValueError("ragged batches: a zstd dictionary goes with the uniform-slot layout and the one-wave decoder "
+                             "(no compact_scratch, no split_decode)")
+        if dictionary is not None and not zdict and (codec != "lz4" and codec != "lz4fast" or compact):
+            raise ValueError("ragged batches: a dictionary goes with codec lz4 / lz4fast / zstd / zstd_fast and the "
+                             "uniform-slot layout (compact=False)")
         # the variant, chosen once: the compress and decompress calls (their names go into the error texts), each with
         # the arguments it takes before the chunk arrays, and the sizing call; the compact layouts take the batch's
         # total too (sizing: after the codec or level; compress: after max_chunk_bytes, and max_total as it is then:
         # a caller may lower its promise between calls)
         self._promise = compact or compact_scratch
-        if self.zstd:
+        if zdict:   # (3f: the zstd dictionary's own calls; the tensor is kept with 16 readable bytes after it)
+            nd = int(dictionary.numel())
+            ct = L.lzh_zstd_dict_compress_temp_bytes(self.level, nd, max_chunk_bytes, max_chunks)
+            dt = L.lzh_zstd_dict_decompress_temp_bytes(nd, max_chunk_bytes, max_chunks)
+            if ct == 0 or dt == 0:
+                raise ValueError(f"ragged batches: zstd level {self.level} (1, -1 .. -5) / a dictionary of {nd} bytes "
+                                 f"(8 .. 131072) / chunks of {max_chunk_bytes} bytes (up to 131072) are not supported")
+            flat = dictionary.reshape(-1)
+            if bytes(flat[:4].cpu().numpy().tobytes()) == b"\x37\xa4\x30\xec":   # (read once, here)
+                raise ValueError("ragged batches: the dictionary begins with zstd's dictionary magic; trained "
+                                 "dictionaries are not supported (the bytes would be used as content)")
+            dev = device or torch.device("cuda", torch.cuda.current_device())
+            self.dictionary = torch.zeros(nd + 16, dtype=torch.uint8, device=dev)
+            self.dictionary[:nd].copy_(flat)
+            self._compress, self._decompress = L.lzh_zstd_compress_ragged_dict_async, L.lzh_zstd_decompress_ragged_dict_async
+            self._chead, self._dhead = (self.level, self.dictionary.data_ptr(), nd), (self.dictionary.data_ptr(), nd)
+            sizing = None
+        elif self.zstd:
             if dfast:
                 self._compress = (L.lzh_zstd_dfast_compress_ragged_compact_async if compact_scratch
                                   else L.lzh_zstd_dfast_compress_ragged_async)

@@ -520,6 +520,73 @@ int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, 
         });
 }
 
+// ---- 3f. ragged zstd batches with a shared dictionary: zstd_dict_temp / ragged_decode_temp, the checks and the
+// scan -> pack of 3c ----
+static bool zstd_dict_sizes_ok(size_t dict_bytes, size_t max_chunk_bytes) {
+    return dict_bytes >= 8 && dict_bytes <= kZstdDictMax && max_chunk_bytes <= kZstdDictMax;
+}
+static bool zstd_dict_ok(int level, size_t dict_bytes, size_t max_chunk_bytes) {
+    return (level == 1 || (level <= -1 && level >= -5)) && zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes);
+}
+
+size_t lzh_zstd_dict_compress_temp_bytes(int level, size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_dict_ok(level, dict_bytes, max_chunk_bytes) ? zstd_dict_temp(dict_bytes, nchunks, max_chunk_bytes).total : 0;
+}
+
+size_t lzh_zstd_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes) ? ragged_decode_temp(nchunks).total : 0;
+}
+
+int lzh_zstd_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes, const void* const* d_in_ptrs,
+                                        const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes,
+                                        void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
+                                        void* d_temp, size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool ok = zstd_dict_ok(level, dict_bytes, max_chunk_bytes);
+    const ZstdDictTemp t = ok ? zstd_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    return ragged_compress(
+        ok, nchunks, d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total,
+        temp_bytes, d_csizes, d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs, d_in_bytes,
+                                        max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k, base + t.recs,
+                                        t.rec_stride, s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
+}
+
+int lzh_zstd_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
+                                          size_t packed_readable, const uint32_t* d_csizes, const uint64_t* d_offsets,
+                                          void* const* d_out_ptrs, const uint64_t* d_out_bytes, size_t nchunks,
+                                          size_t max_chunk_bytes, int32_t* d_status, void* d_temp, size_t temp_bytes,
+                                          void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return ragged_decompress(
+        zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes), nchunks,
+        d_dict && d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp,
+        temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+            return lzh_launch_zstd_dict_decompress((const uint8_t*)d_dict, (uint32_t)dict_bytes, (const uint8_t*)d_packed,
+                                                   packed_readable, offs, d_csizes, d_out_ptrs, d_out_bytes,
+                                                   max_chunk_bytes, d_status, (uint32_t)nchunks, s);
+        });
+}
+
+int lzh_debug_zstd_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out) {
+    if (!out || !zstd_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    return lzh_zstd_dict_params(level, n, dict_bytes, out) ? LZH_OK : LZH_EARG;
+}
+
+long lzh_debug_zstd_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n, uint32_t* seqs,
+                               size_t cap) {
+    if (!dict || (!src && n) || (!seqs && cap) || !zstd_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    return lzh_zstd_dict_host_parse(level, (const uint8_t*)dict, dict_bytes, (const uint8_t*)src, n, seqs, cap);
+}
+
 // ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
 // compress temp: chunk_temp(zstd) of nchunks staging slots and scratch areas sized for max_chunk_bytes;
 // decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors), or

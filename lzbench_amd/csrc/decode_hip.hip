@@ -1727,9 +1727,17 @@ struct FrameState {
     uint64_t clk[kZClk], clk_last;      // (LZH_ZSTD_STATS)
 };
 
+// The second match source of the dictionary calls (zstd_dict_hip.hip: a type with kOn = true, `bytes` and copy()).
+// NoDict: none -- every use below is a compile-time constant and the decoders of this file keep their code.
+struct NoDict {
+    static constexpr bool kOn = false;
+    static constexpr int bytes = 0;
+};
+
 // one compressed block [bs, be) of the frame; output continues at op (returns new op, < 0 error)
+template <class DictT = NoDict>
 __device__ __forceinline__ int decode_block(const Bytes& rin, const Bytes& lout, ZWin& fw, ZWin& lw, ZSink& O, LDSA Lds& L,
-                            FrameState& F, int bs, int be, int op, int fcs, int lane) {
+                            FrameState& F, int bs, int be, int op, int fcs, int lane, const DictT& D = DictT()) {
     // ---- literals section (ZSTD_decodeLiteralsBlock)
     const uint32_t b0 = fbyte(fw, bs, lane);
     const int ltype = (int)(b0 & 3u), sf = (int)((b0 >> 2) & 3u);
@@ -1812,7 +1820,9 @@ __device__ __forceinline__ int decode_block(const Bytes& rin, const Bytes& lout,
     if (nseq > 0) {
         if (p >= be) return ZC;
         const uint32_t modes = fbyte(fw, p++, lane);
-        if (modes & 3u) return ZC;
+        // (the two reserved bits: zstd 1.5.2's ZSTD_decodeSeqHeaders does not look at them; the decoders of this file
+        // have always refused them and keep doing so, the dictionary decoder gives the reference's verdict)
+        if (!DictT::kOn && (modes & 3u)) return ZC;
         ZCLK(F, 0);
         int u = seq_table(fw, p, be, (int)(modes >> 6), 0, L.ll, F.llA, F.llV, L, lane);
         if (u < 0) return ZC;
@@ -1882,9 +1892,17 @@ __device__ __forceinline__ int decode_block(const Bytes& rin, const Bytes& lout,
             const int lrem = lrem0 - lpv - glit;      // literals not yet taken
             const int o0 = opv + opg + gout;          // output position of this sequence
             // (an offset code of 31 gives 2^31 - 3 + bits: compared unsigned, as the reference's size_t)
+            bool far = false;                         // (dictionary calls: the match starts before the output)
+            if constexpr (DictT::kOn) {
+                far = (uint32_t)off > (uint32_t)(o0 + ll);
+                if (ll > lrem || (uint32_t)off > (uint32_t)(o0 + ll) + (uint32_t)D.bytes ||
+                    (int64_t)o0 + ll + ml > (int64_t)(fcsv - (lrem - ll)))
+                    return ZC;
+            } else {
             if (ll > lrem || (uint32_t)off > (uint32_t)(o0 + ll) || (int64_t)o0 + ll + ml > (int64_t)(fcsv - (lrem - ll)))
                 return ZC;
-            const bool big = ll > 255 || ml > 4095;
+            }
+            const bool big = ll > 255 || ml > 4095 || far;
             if (big || k == LZH_WAVE || glit + ll > 384) {
                 // emit the pending group
                 if (k > 0) {
@@ -1904,7 +1922,14 @@ __device__ __forceinline__ int decode_block(const Bytes& rin, const Bytes& lout,
                     const int bl = unii(ll), bm = unii(ml), bo = unii(off), lpu = unii(lpv), opu = unii(op + opg);
                     ZCLK(F, 4);
                     O.literals(lw, lsrc, lpos + lp + lpu, opu, bl, lane);
+                    if constexpr (DictT::kOn) {
+                        // dictionary bytes first, then the output's own from its first byte on
+                        const int back = bo - (opu + bl), dn = back > 0 ? min(back, bm) : 0;
+                        if (dn > 0) D.copy(O, opu + bl, back, dn, lane);
+                        if (bm > dn) O.match(opu + bl + dn, bo, bm - dn, lane);
+                    } else {
                     O.match(opu + bl, bo, bm, lane);
+                    }
                     ZCLK(F, 6);
                     opg += ll + ml;
                     lpv += ll;
@@ -1951,8 +1976,9 @@ __device__ __forceinline__ int decode_block(const Bytes& rin, const Bytes& lout,
 // one frame in rin[0, cs) -> out[0, cap): returns the decoded size or an error code
 // lout: the output region for reading decoded literals back (whole dwords: its range ends at
 // the dword holding the last byte, so no load that straddles the end reads back as zero)
+template <class DictT = NoDict>
 __device__ __forceinline__ int decode_frame(const Bytes& rin, const Bytes& lout, int cs, ZSink& O, LDSA Lds& L, int cap,
-                            int lane, unsigned long long* stats) {
+                            int lane, unsigned long long* stats, const DictT& D = DictT()) {
     ZWin fw;
     fw.bind(rin, nullptr);
     fw.load(0, lane);
@@ -2009,7 +2035,7 @@ __device__ __forceinline__ int decode_frame(const Bytes& rin, const Bytes& lout,
             p += 1;
         } else if (type == 2) {
             if (p + bsz > cs) return ZC;
-            const int r = decode_block(rin, lout, fw, lw, O, L, F, p, p + bsz, op, n, lane);
+            const int r = decode_block(rin, lout, fw, lw, O, L, F, p, p + bsz, op, n, lane, D);
             if (r < 0) return r;
             op = r;
             p += bsz;

@@ -214,6 +214,32 @@ hipError_t lzh_launch_zstd_dfast_compact(const void* const* in_ptrs, const uint6
 LzhCompactRegions lzh_zstd_dfast_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks);
 LzhCompactRegions lzh_zstd_dfast_compact_slot(uint64_t n);
 
+// ragged zstd batches with a shared dictionary (zstd_dict_hip.hip, zstd_dict_parse.h; include/lzbench_hip.h 3f):
+// dict_bytes in 8 .. 131072 and max_bytes <= 131072, 16 readable bytes after the dictionary; levels 1, -1 .. -5.
+// lzh_zstd_dict_scratch_stride: a chunk's scratch area (the areas of the zstd kernels' Layout for a block of max_bytes,
+// then the frame's own copy of its class's table); lzh_zstd_dict_tables_bytes: the table region (one filled table per
+// (hashLog, minMatch) class a batch can take, a constant bound).  The compress launcher fills the class tables once,
+// then runs the match kernel and the entropy stage of lzh_launch_zstd_entropy_ragged (zstd_ragged_hip.hip), every
+// launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 / status[i] = -1.
+size_t lzh_zstd_dict_scratch_stride(size_t dict_bytes, size_t max_bytes);
+size_t lzh_zstd_dict_tables_bytes(void);
+hipError_t lzh_launch_zstd_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const void* const* in_ptrs,
+                                const uint64_t* in_bytes, uint64_t max_bytes, int level, uint8_t* stage, uint64_t stride,
+                                uint32_t* csizes, uint32_t nchunks, uint8_t* scratch, uint64_t fstride, hipStream_t s);
+hipError_t lzh_launch_zstd_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                          uint8_t* scratch, uint64_t fstride, uint64_t seq_off, uint64_t lit_off,
+                                          uint64_t att_off, uint64_t tmp_off, hipStream_t s);
+hipError_t lzh_launch_zstd_dict_decompress(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed,
+                                           uint64_t packed_readable, const uint64_t* offsets, const uint32_t* csizes,
+                                           void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
+                                           int32_t* status, uint32_t nchunks, hipStream_t s);
+// host arithmetic for the debug calls: ZSTD_getParams(level, n, dict_bytes) as {windowLog, hashLog, minMatch,
+// targetLength, block size}, and the host walk of one chunk ((ll, ml, offBase) triples; the count, -1: arguments)
+int lzh_zstd_dict_params(int level, uint64_t n, uint64_t dict_bytes, uint32_t* out);
+long lzh_zstd_dict_host_parse(int level, const uint8_t* dict, uint64_t dict_bytes, const uint8_t* src, uint64_t n,
+                              uint32_t* seqs, uint64_t cap);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

@@ -81,6 +81,25 @@ static inline DictTemp lz4_dict_temp(size_t k, size_t chunk) {
     return t;
 }
 
+// ---- zstd compression of k chunks of up to `chunk` bytes with a shared dictionary (3f): the staging slots of
+// chunk_temp(zstd), then k scratch areas of the dictionary calls' own stride (the zstd kernels' areas for a block of
+// `chunk` bytes and the frame's copy of its class's table, the largest any frame of the batch can take), then the
+// table region: one filled table per (hashLog, minMatch) class, a constant bound (lzh_zstd_dict_tables_bytes).
+static const size_t kZstdDictMax = (size_t)131072;      // largest dictionary and largest chunk of the dictionary calls
+struct ZstdDictTemp { size_t stride, rec_stride, stage, recs, tabs, total; };
+static inline ZstdDictTemp zstd_dict_temp(size_t dict_bytes, size_t k, size_t chunk) {
+    ZstdDictTemp t;
+    TempCursor c;
+    chunk = std::max<size_t>(chunk, 1);                 // (a batch of empty chunks is laid out as one of 1-byte chunks)
+    t.stride = lzh_stage_stride(LZH_CODEC_ZSTD, chunk);
+    t.rec_stride = lzh_zstd_dict_scratch_stride(dict_bytes, chunk);
+    t.stage = c.take(k * t.stride, kGap);
+    t.recs = c.take(k * t.rec_stride, kGap);
+    t.tabs = c.take(lzh_zstd_dict_tables_bytes(), kGap);
+    t.total = c.at;
+    return t;
+}
+
 // ---- framed compression: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes:
 //   staging slots | LZ4 sequence records of the blocks, then 8 bytes per block (linked frames: the per-frame
 //   table snapshots instead) | block sizes | block offsets inside their frame
