@@ -1,10 +1,12 @@
 """GPU: zstd ragged batches with a shared dictionary (include/lzbench_hip.h 3f, RaggedCodec("zstd", dictionary=...))
 against the reference build's own ZSTD_compress_usingDict and ZSTD_decompress_usingDict (tests/zstd_dict_ref.py),
-byte for byte.  Run with -m gpu."""
+byte for byte; and the decoder on the hand-built frames of tests/zstd_dict_frames.py, whose expected bytes are that
+module's pure-Python model (tests/test_zstd_dict_frames.py holds the model to the reference).  Run with -m gpu."""
 import numpy as np
 import pytest
 
 import lzbench_amd as L
+import zstd_dict_frames as F
 import zstd_dict_inputs as I
 import zstd_dict_ref as R
 
@@ -296,6 +298,99 @@ def test_small_json_records_pack_smaller_with_the_dictionary(torch_cuda):
     assert with_dict == ref_dict and alone == ref_alone
     assert with_dict < alone
     roundtrip(torch, rc, host, offs, sizes)
+
+
+# ---- the hand-built frames (tests/zstd_dict_frames.py): every path of a sequence whose source is the dictionary --
+def decode_frames(torch, rc, frames, caps):
+    """(statuses, the whole output buffer, offsets) of one decode call over hand-made frames, chunk i caps[i] bytes"""
+    offs, total = layout(caps)
+    out = torch.full((total,), 0xEE, dtype=torch.uint8, device="cuda")
+    packed = np.frombuffer(b"".join(frames), np.uint8)
+    rc.decompress(out, offs, caps, packed=to_dev(torch, packed, 256),
+                  csizes=torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda"))
+    torch.cuda.synchronize()
+    return rc.status[: len(frames)].cpu().numpy(), out.cpu().numpy(), offs
+
+
+@pytest.mark.parametrize("residue", [0, 1, 2, 3])
+def test_hand_frames_decode(torch_cuda, residue):
+    """one batch of every accepting frame; the expected bytes are the pure-Python model's"""
+    torch = torch_cuda
+    d = F.dictionary()
+    acc = F.accepting()
+    frames, caps = [f for _, f, _, _ in acc], [len(c) for _, _, c, _ in acc]
+    rc = codec(torch, d, max(caps), len(acc), residue=residue)
+    st, got, offs = decode_frames(torch, rc, frames, caps)
+    assert sorted(set(int(o) % 4 for o in offs)) == [0, 1, 2, 3]
+    mask = np.zeros(len(got), bool)
+    bad = []
+    for i, (name, _, content, _) in enumerate(acc):
+        o = int(offs[i])
+        mask[o: o + caps[i]] = True
+        if int(st[i]) != len(content):
+            bad.append(f"{name}: status {st[i]}, content {len(content)}")
+        elif got[o: o + caps[i]].tobytes() != content:
+            diff = np.flatnonzero(got[o: o + caps[i]] != np.frombuffer(content, np.uint8))
+            bad.append(f"{name}: {len(diff)} bytes differ, the first at {diff[0]}")
+    assert not bad, "; ".join(bad)
+    assert (got[~mask] == 0xEE).all(), "the decoder wrote outside the chunks"
+
+
+def test_hand_frames_rejected(torch_cuda):
+    """one call with the dictionary a byte shorter at its front: the frame that copies the whole dictionary now asks
+    for a byte before it, and a dictionary ID other than 0 names another dictionary; nothing outside a chunk's own
+    range is written"""
+    torch = torch_cuda
+    d = F.dictionary()
+    assert len({cut for _, cut in F.REJECTS}) == 1
+    short = np.ascontiguousarray(d[F.REJECTS[0][1]:])
+    byname = {n: (f, c) for n, f, c, _ in F.frames()}
+    frames, caps = [byname[n][0] for n, _ in F.REJECTS], [len(byname[n][1]) for n, _ in F.REJECTS]
+    assert all(F.expected(n, short)[0] < 0 for n, _ in F.REJECTS)
+    rc = codec(torch, short, max(caps), len(frames), residue=1)
+    st, got, offs = decode_frames(torch, rc, frames, caps)
+    assert all(int(s) < 0 for s in st), st
+    mask = np.zeros(len(got), bool)
+    for o, s in zip(offs, caps):
+        mask[int(o): int(o) + s] = True
+    assert (got[~mask] == 0xEE).all(), "a rejected frame wrote outside its chunk"
+
+
+def test_reserved_mode_bits_on_the_plain_decoder(torch_cuda):
+    """today's documented difference: the ragged zstd decoder without a dictionary refuses a reserved bit of the
+    sequence-modes byte, the dictionary decoder (test_hand_frames_decode) gives the reference's verdict"""
+    torch = torch_cuda
+    byname = {n: (f, c) for n, f, c, _ in F.frames()}
+    frames = [byname[n][0] for n in F.NEEDS_NO_DICTIONARY]
+    caps = [len(byname[n][1]) for n in F.NEEDS_NO_DICTIONARY]
+    rc = L.RaggedCodec("zstd", max(caps), len(frames), 1)
+    st, got, offs = decode_frames(torch, rc, frames, caps)
+    assert all(int(s) < 0 for s in st), st
+    # the same frame with the bit cleared decodes: the bit alone is what the decoder refuses
+    twin, content = F.reserved_plain_cleared()
+    assert content == byname["reserved-bit0-plain"][1] and len(twin) == len(frames[0])
+    assert sum(a != b for a, b in zip(twin, frames[0])) == 1
+    clean = [twin]
+    st, got, offs = decode_frames(torch, rc, clean, caps)
+    for i, n in enumerate(F.NEEDS_NO_DICTIONARY):
+        assert int(st[i]) == caps[i] and got[offs[i]: offs[i] + caps[i]].tobytes() == byname[n][1], n
+
+
+@pytest.mark.parametrize("level", [-1, -2, -4, -5])
+def test_the_other_levels(torch_cuda, level):
+    """levels -1, -2, -4 and -5 (targetLength, the parse's step): the constructed pairs and three chunks of one text
+    dictionary, byte for byte against the reference, and back"""
+    R.need()
+    torch = torch_cuda
+    dt = I.dictionary("text", 4095)
+    batches = [(d, [c]) for d, c in I.constructed().values()]
+    batches.append((dt, [I.chunk("text", s) for s in (300, 4099, 16385)]))
+    for j, (d, parts) in enumerate(batches):
+        host, offs, sizes = place(parts)
+        rc = codec(torch, d, max(sizes), len(parts), level, residue=j % 4)
+        rc.compress(to_dev(torch, host), offs, sizes)
+        check_batch(torch, rc, d, parts, level)
+        roundtrip(torch, rc, host, offs, sizes)
 
 
 def test_zz_graph_replay(torch_cuda):

@@ -108,6 +108,16 @@ def test_constructed_cases_reach_their_branches():
     assert check(1, d, c)[-1][2] - 3 == len(d) + len(c) - 20 == 262124, "chunk end to dictionary start"
 
 
+@pytest.mark.parametrize("level", [-1, -2, -4, -5])
+def test_host_walk_at_the_other_levels(level):
+    """the inputs of tests/test_gpu_zstd_dict.py's test_the_other_levels (targetLength is the parse's step)"""
+    R.need()
+    for d, c in I.constructed().values():
+        check(level, d, c)
+    dt = I.dictionary("text", 4095)
+    assert sum(len(check(level, dt, I.chunk("text", s))) for s in (300, 4099, 16385)) > 0
+
+
 def test_separate_and_adjacent_dictionary_give_other_bytes():
     """the reference runs another parser when the chunk starts where the dictionary ends: the helper must not do that"""
     R.need()

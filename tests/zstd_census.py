@@ -92,7 +92,7 @@ def _literals(c, b: bytes):
     return size, regen
 
 
-def _sequences(c, b: bytes):
+def _sequences(c, b: bytes, reserved_ok=False):
     """the sequences section (the rest of a block): its count; the tables and the bitstream are not decoded"""
     _need(len(b) >= 1, "no sequences section")
     b0 = b[0]
@@ -111,7 +111,7 @@ def _sequences(c, b: bytes):
     c["nseq/1-127" if p == 1 else "nseq/128-32511" if p == 2 else "nseq/long"] += 1
     _need(len(b) > p, "no table-mode byte")
     m = b[p]
-    _need(not m & 3, "reserved table-mode bits")
+    _need(reserved_ok or not m & 3, "reserved table-mode bits")
     rle = 0
     for name, shift in (("LL", 6), ("OF", 4), ("ML", 2)):
         mode = (m >> shift) & 3
@@ -122,8 +122,9 @@ def _sequences(c, b: bytes):
     return nseq
 
 
-def walk(frame: bytes):
-    """(Counter of classes, [(regen_size, nseq) per compressed block], content size or None)"""
+def walk(frame: bytes, reserved_ok=False):
+    """(Counter of classes, [(regen_size, nseq) per compressed block], content size or None); reserved_ok: the two
+    reserved bits of a table-mode byte may be set (zstd 1.5.2 does not look at them)"""
     frame = bytes(frame)
     c = Counter()
     p, fcs, checksum = frame_header(frame)
@@ -149,7 +150,7 @@ def walk(frame: bytes):
             _need(p + bsz <= len(frame), "compressed block past the end")
             body = frame[p:p + bsz]
             lsz, regen = _literals(c, body)
-            nseq = _sequences(c, body[lsz:])
+            nseq = _sequences(c, body[lsz:], reserved_ok)
             blocks.append((regen, nseq))
             p += bsz
         _need(p <= len(frame), "block past the end")
