@@ -18,10 +18,10 @@
 //                                    (zstdd::decode_frame's DictT): an offset may reach dict_bytes before the chunk's
 //                                    first byte; such a sequence copies dictionary bytes, then output bytes.
 //
-// zstdc_hip.hip and decode_hip.hip are included for their device functions alone; nothing here changes their kernels.
+// zstdc_hip.hip is included for its device functions alone, the decoder's are zstdd.h; neither's kernels change.
 #define LZH_DEVICE_FUNCTIONS_ONLY 1
 #include "zstdc_hip.hip"
-#include "decode_hip.hip"
+#include "zstdd.h"
 #include "zstd_dict_parse.h"
 
 namespace zdd {
@@ -178,9 +178,6 @@ lzh_zstd_dict_match_kernel(const uint8_t* dict, uint32_t dict_bytes, const uint8
     }
 }
 
-#ifndef LZH_ZSTD_MINW
-#define LZH_ZSTD_MINW 1   // waves per SIMD the register allocation must allow (as lzh_zstd_decompress_kernel)
-#endif
 extern "C" __global__ void __launch_bounds__(64, LZH_ZSTD_MINW)
 lzh_zstd_dict_decompress_kernel(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed, uint64_t packed_readable,
                                 const uint64_t* offsets, const uint32_t* csizes, void* const* out_ptrs,

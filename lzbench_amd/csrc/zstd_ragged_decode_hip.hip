@@ -5,15 +5,12 @@
 // lookup: ragged_span (common.h) loads chunk blockIdx.x's output pointer and size once and makes them
 // wave-uniform; what follows is that kernel's body (zstdd::decode_frame, a plain copy for a chunk stored raw).
 // The frame is read and the output written through buffer descriptors of the frame's and the chunk's own sizes,
-// so a malformed frame or a wrong size writes nothing outside the chunk.  decode_hip.hip is included for its
-// device functions alone (and compiled with its flags); nothing here changes the uniform decoders' code.
+// so a malformed frame or a wrong size writes nothing outside the chunk.  The decoder's device code is zstdd.h,
+// compiled here with decode_hip.hip's flags; nothing here changes the uniform decoders' code.
 // A chunk whose device-side size passes max_bytes is not decoded: status -1, no byte written.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "decode_hip.hip"
+#include "decode_win.h"
+#include "zstdd.h"
 
-#ifndef LZH_ZSTD_MINW
-#define LZH_ZSTD_MINW 1   // waves per SIMD the register allocation must allow (as lzh_zstd_decompress_kernel)
-#endif
 extern "C" __global__ void __launch_bounds__(64, LZH_ZSTD_MINW)
 lzh_zstd_decompress_ragged_kernel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                   const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,

@@ -309,9 +309,6 @@ __device__ __forceinline__ void lit_copy(const Bytes& src, int s0, const Bytes& 
     if (tl) dst.st8(d0 + t0 + lane, tb);
 }
 
-#ifndef LZH_ZSTD_PREF
-#define LZH_ZSTD_PREF 1   // the first batch's loads issued with the previous sequence's table fills
-#endif
 #ifndef LZH_ZSTD_FWD
 #define LZH_ZSTD_FWD 16   // lanes of the forward compare in the match's round trip (4 bytes each; longer: count_fwd)
 #endif
@@ -382,7 +379,7 @@ __device__ void fast_block(const Tab& T, const Bytes& in, const ZParams& P, int 
         bool ended = false;
         Sched S;
         PLoad Ld;
-        if (LZH_ZSTD_PREF && pre) {
+        if (pre) {
             S = S0;
             Ld = L0;
         } else {
@@ -555,11 +552,10 @@ __device__ void fast_block(const Tab& T, const Bytes& in, const ZParams& P, int 
         {   // table fills (zstd_fast.c:216-231) and the immediate repcode check: loads in one round trip
             const uint64_t h1 = ld64(in, ip1), h2 = ld64(in, cur0 + 2), h3 = ld64(in, ip - 2);
             const uint32_t c0 = in.w32(ip), c1 = in.w32(ip - (int)r2);
-            if (LZH_ZSTD_PREF) {   // (unconditional: past ilimit the loop ends and they go unused)
-                S0 = sched(ip, (int)P.step, (int)P.step, ip + 128);
-                L0 = pload(S0, ip);
-                pre = true;
-            }
+            // the next first batch's loads, with the fills (unconditional: past ilimit the loop ends, they go unused)
+            S0 = sched(ip, (int)P.step, (int)P.step, ip + 128);
+            L0 = pload(S0, ip);
+            pre = true;
             if (lane == 0) {
                 if (ip1 < ip) T.put(zh<kMls>(h1, P.hlog, P.mls), (uint32_t)ip1 + 1);
                 if (ip <= ilimit) {
@@ -589,10 +585,6 @@ __device__ void fast_block(const Tab& T, const Bytes& in, const ZParams& P, int 
     copy_span(in, anchor, O.lits, O.nl, be - anchor, lane, LZH_WAVE);   // last literals
     O.nl += be - anchor;
 }
-
-#ifndef LZH_ZSTD_TAB17
-#define LZH_ZSTD_TAB17 1   // 17-bit hash-table entries (LdsTab17) for chunks <= 128 KiB
-#endif
 
 #if LZH_ZSTDC_STATS
 // entropy-kernel phase clocks (indices 16..23): lane 0 adds the clocks since its previous mark
@@ -1699,7 +1691,7 @@ uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size) {
     const uint32_t ebytes = chunk_size < (16u << 20) ? 3u : 4u;
     const uint32_t t17 = (2u << PF.hlog) + std::max((1u << PF.hlog) / 8u, 4u);
     return (4u << PF.hlog) > (uint32_t)LZH_ZSTD_LDS_MAX ? 0u
-           : (LZH_ZSTD_TAB17 && chunk_size <= 131072u) ? ((t17 + 15u) & ~15u) : (ebytes << PF.hlog);
+           : chunk_size <= 131072u ? ((t17 + 15u) & ~15u) : (ebytes << PF.hlog);
 }
 
 hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,

@@ -30,7 +30,7 @@
     const uint32_t nent = 1u << P.hlog;
     const uint32_t lds_table_bytes = lds_arg;          // the table's bytes in dynamic LDS (0: global)
     const uint32_t bmb = max(nent / 8u, 4u);            // LdsTab17 bitmap bytes
-    if (LZH_ZSTD_TAB17 && chunk_size <= 131072u && nblocks == 1 && 2u * nent + bmb <= lds_table_bytes) {
+    if (chunk_size <= 131072u && nblocks == 1 && 2u * nent + bmb <= lds_table_bytes) {
         // (single-block frames: the table starts empty and is not saved)
         LdsTab17 T{(LDSA uint16_t*)zlds, (LDSA uint32_t*)((LDSA uint8_t*)zlds + 2 * nent)};
         for (uint32_t i = lane; i < (2u * nent + bmb) / 4u; i += 64) ((volatile LDSA uint32_t*)zlds)[i] = 0u;

@@ -9,7 +9,7 @@ union (tests/lz_census.py) of what ran is printed once.  Run with -m gpu.
 
 Found by these streams: an LZ4 match at an offset under 64 that is no power of two and longer than the output window
 less that offset (the generated stream random-65536-2: offset 62, 10061 bytes, first wrong byte 4096 into the match
-under the 4 KiB window) decoded wrong with a success status.  owin::SinkT::match (lzbench_amd/csrc/decode_hip.hip)
+under the 4 KiB window) decoded wrong with a success status.  owin::SinkT::match (lzbench_amd/csrc/decode_win.h)
 read such a match's bytes from the one period before it for its whole length, and from KW - offset bytes on the match
 itself had come round the window onto that period.  Powers of two hid it: there the bytes that come round are the
 ones they replace, so runs of one byte never showed it.  The cases long-overlap-match@KW stay as its tests."""

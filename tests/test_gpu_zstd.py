@@ -1,4 +1,4 @@
-"""GPU zstd decoder (LZH_CODEC_ZSTD, decode_hip.hip zstdd::) on frames written by the REFERENCE
+"""GPU zstd decoder (LZH_CODEC_ZSTD, zstdd.h zstdd::) on frames written by the REFERENCE
 zstd 1.5.2 with lzbench's zstd-row parameters (compressors.cpp:1745-1773): the committed golden
 frames, fresh frames over corpora x chunk sizes x levels (raw, RLE and compressed blocks,
 predefined / RLE / FSE / repeat tables, 1- and 4-stream Huffman literals, multi-block frames),

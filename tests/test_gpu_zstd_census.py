@@ -8,7 +8,7 @@ of what ran is printed once.  Run with -m gpu.
 Found by these inputs: `tail_repeat` (a 61072-byte match at offset 70000) and `rle_literals` (a 131072-byte match at
 offset 131072) decoded wrong on every path -- a match whose source is out of the LDS output window and that does
 not overlap itself was written through the window without a flush, so one longer than the window wrapped it
-(owin::SinkT::match, lzbench_amd/csrc/decode_hip.hip).  Both stay here as its tests."""
+(owin::SinkT::match, lzbench_amd/csrc/decode_win.h).  Both stay here as its tests."""
 from collections import Counter
 
 import numpy as np

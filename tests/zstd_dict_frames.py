@@ -14,7 +14,7 @@ present, must agree frame by frame (tests/test_zstd_dict_frames.py).
 Builder.trace lists what the decoder executes: Ev(pos, ll, ml, off, rep, blk) per sequence (pos: the content position
 where its literals start; rep: the offset came from a repeat code; blk: the block's index), and the same with ml = 0
 for a raw block and for a block's last literals.  classify() names the decoder's cases over such a trace, from the
-thresholds of lzbench_amd/csrc/decode_hip.hip: the 2 KiB LDS output window (kZW), a window match's reach (kZW - 128),
+thresholds of lzbench_amd/csrc/zstdd.h: the 2 KiB LDS output window (kZW), a window match's reach (kZW - 128),
 literal runs above 512 bytes that bypass the window (and move ringlo), copy rounds of 64 bytes."""
 from collections import namedtuple
 
