@@ -24,12 +24,10 @@
 //                                 overlapping ones and the ones that follow a start in the dictionary into the
 //                                 output -- is read from memory written by an earlier sequence, or from the
 //                                 dictionary's end where that position is negative.
-// This is not the speculative batch parse of lz4c_hip.hip (compress_chunk): that function's candidate window, slow
+// This is not the speculative batch parse of lz4c.h (compress_chunk): that function's candidate window, slow
 // paths and input ring address one buffer, and the two-source M side is not built into it yet.  The
-// device functions of lz4c_hip.hip are included for the hash, the sequence layout and the span copy alone; no kernel
-// of another file changes.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "lz4c_hip.hip"
+// header is included for the hash, the sequence layout and the span copy alone; no kernel of another file changes.
+#include "lz4c.h"
 
 namespace lz4d {
 

@@ -16,10 +16,9 @@
 // expression changes the uniform kernels' schedule and with it their code hashes -- so here rec_stride and
 // stride are CompactSlot values (ragged_slots.h): chunk * slot is the slot's scanned offset, an explicit cast of it to an integer
 // type the slot's own size (the two forms the bodies use; nothing else compiles).  The buffer descriptors the bodies build are therefore bounded by the chunk's own slot.
-// As in ragged_hip.hip the two codec files are included for their device functions alone.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "lz4c_hip.hip"
-#include "snappyc_hip.hip"
+// As in ragged_hip.hip the two codecs' device functions come from their headers.
+#include "lz4c.h"
+#include "snappyc.h"
 #include "launch.h"
 #include "ragged_slots.h"
 

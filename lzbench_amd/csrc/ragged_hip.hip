@@ -6,18 +6,17 @@
 // once and makes them wave-uniform, and the kernel body that follows is the uniform kernel's, shared as
 // text (the *_body.inc files) under the names the uniform kernels use: in + off is the chunk's address
 // (off = 0 here), in_readable - off the bytes that may be read from it (n + 16 here), n its size.
-// The two codec files are included for their device functions alone, so every function has the one
-// caller per code object that it has in its own file and is inlined as it is there.  Nothing here
-// changes the uniform kernels' code (profiles/traffic*.json are keyed to their code hashes).
+// The two codecs' device functions come from their headers (lz4c.h, snappyc.h), so every function has the
+// one caller per code object that it has in its codec's own unit and is inlined as it is there.  Nothing
+// here changes the uniform kernels' code (profiles/traffic*.json are keyed to their code hashes).
 //
 // Every slot (staging, records) is sized for the batch's max_bytes and reached through a buffer
 // descriptor of that size.  A chunk whose device-side size passes max_bytes is not processed: no kernel
 // touches its slots, its compressed size is 0.  Decoding reuses the block decoder's 32-byte descriptors
 // (decode_hip.hip decompress_chunk): lzh_ragged_desc_kernel fills one per chunk with the chunk's
 // absolute output address as the destination offset.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "lz4c_hip.hip"
-#include "snappyc_hip.hip"
+#include "lz4c.h"
+#include "snappyc.h"
 
 // ----------------------------------------------------------------------------------------- LZ4
 extern "C" __global__ void __launch_bounds__(64)

@@ -10,7 +10,7 @@
 #define LZH_HD __host__ __device__ __forceinline__
 
 constexpr int kLzhSlotLz4 = 0, kLzhSlotSnappy = 1;          // = LZH_CODEC_LZ4, LZH_CODEC_SNAPPY
-constexpr uint64_t kLzhSnFragRecBytes = (16384 + 32) * 8;   // = kFragRecs * 8 (snappyc_hip.hip), a multiple of 256
+constexpr uint64_t kLzhSnFragRecBytes = (16384 + 32) * 8;   // = kFragRecs * 8 (snappyc.h), a multiple of 256
 
 LZH_HD uint64_t lzh_slot_align(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
 

@@ -1,11 +1,15 @@
-"""Layout of lzbench_amd/csrc: the decoders' shared device code is in headers (decode_win.h, zstdd.h), and the
-switches retired with that move stay out.  Reads the sources only.
+"""Layout of lzbench_amd/csrc: the decoders' shared device code is in headers (decode_win.h, zstdd.h), so is that of
+the LZ4 and snappy compressors (lz4c.h, snappyc.h), and the switches retired with the first move stay out.  Reads the
+sources only; the one compile is a syntax check of each compressor header on its own.
 
 The ragged split decoder is the exception for now: zstd_ragged_split_hip.hip is the file it was, still includes
 decode_hip.hip under LZH_DEVICE_FUNCTIONS_ONLY and keeps its own LZH_ZSTD_MINW block; the split decoder's device code
 stays in decode_hip.hip until that unit moves (profiles/decode_headers/README.md)."""
 import os
 import re
+import subprocess
+
+import pytest
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lzbench_amd", "csrc")
 SPLIT_UNIT = "zstd_ragged_split_hip.hip"
@@ -45,3 +49,50 @@ def test_retired_switches_stay_out():
     for f, s in _sources().items():
         for name in ("LZH_DEC_RING", "LZH_ZSTD_PREF", "LZH_ZSTD_TAB17"):
             assert name not in s, (f, name)
+
+
+# The LZ4 and snappy compressors: device code in lz4c.h and snappyc.h, which the codecs' own units and the ragged,
+# compact and dictionary units include.  (The zstd compressor, zstdc_hip.hip, is still included as text.)
+COMPRESS_HEADERS = ("lz4c.h", "snappyc.h")
+COMPRESS_UNITS = ("lz4c_hip.hip", "snappyc_hip.hip")
+
+
+def test_no_unit_includes_the_lz4_or_snappy_compressor_file():
+    for f, s in _sources().items():
+        for unit in COMPRESS_UNITS:
+            assert not re.search(r'#\s*include\s*"%s"' % re.escape(unit), s), (f, unit)
+
+
+def test_compress_header_units_know_no_include_mode():
+    src = _sources()
+    for f in COMPRESS_UNITS + ("ragged_hip.hip", "ragged_compact_hip.hip", "lz4_dict_hip.hip") + COMPRESS_HEADERS:
+        assert "LZH_DEVICE_FUNCTIONS_ONLY" not in src[f], f
+    for f in ("lz4c_hip.hip", "ragged_hip.hip", "ragged_compact_hip.hip", "lz4_dict_hip.hip"):
+        assert '#include "lz4c.h"' in src[f], f
+    for f in ("snappyc_hip.hip", "ragged_hip.hip", "ragged_compact_hip.hip"):
+        assert '#include "snappyc.h"' in src[f], f
+
+
+def test_makefile_names_no_compressor_file_as_a_prerequisite():
+    """The two files stand in the Makefile only as the sources of their own objects (the pattern rule)."""
+    text = re.sub(r"\\\n", " ", _sources()["Makefile"])
+    for line in text.splitlines():
+        if line.startswith(("#", "\t")) or ":" not in line:
+            continue
+        target, _, prereq = line.partition(":")
+        if prereq.startswith("="):   # (a `:=` assignment)
+            continue
+        for unit in COMPRESS_UNITS:
+            assert unit not in prereq.split(), line
+
+
+@pytest.mark.parametrize("header", COMPRESS_HEADERS)
+def test_compress_header_compiles_when_included_first(header, tmp_path):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc: cannot compile the header")
+    unit = tmp_path / "first.hip"
+    unit.write_text('#include "%s"\n' % header)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", CSRC, str(unit)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr

@@ -6,7 +6,7 @@ with a round trip; and the parse kernel's own event counters (lzh_debug_lz4_stat
 comparison is exact.  The census of what ran is printed once.  Run with -m gpu.
 
 Found by these inputs: `zeros600000` failed on every path before the kernel fix (2371 bytes where the reference
-writes 2363).  The parse's slow count (slow_count, finish_match; lzbench_amd/csrc/lz4c_hip.hip) stopped after 1024
+writes 2363).  The parse's slow count (slow_count, finish_match; lzbench_amd/csrc/lz4c.h) stopped after 1024
 steps of 256 bytes, so a match ran no further than 262164 bytes past its seed where LZ4_count stops only at
 matchlimit: the match was cut and a re-test sequence followed it.  `zeros16m` passes the same cap in the fused
 kernel (chunks over 16 MiB).  The catch-up loops of the kernels that catch up in the parse (the fused kernel,
