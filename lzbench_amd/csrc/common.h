@@ -11,18 +11,6 @@
 
 #define LZH_WAVE 64
 
-// File-scope device variables (constant tables, debug counters) of a codec file: external in the file's own
-// object; internal where another translation unit includes the file for its device functions alone
-// (LZH_DEVICE_FUNCTIONS_ONLY), so that the host-side shadows of the two objects do not collide at link time.
-// Two files are still included that way: zstdc_hip.hip (by zstdc_dfast_hip.hip, zstd_ragged_hip.hip,
-// zstd_ragged_compact_hip.hip, zstd_dict_hip.hip and, through zstdc_dfast_hip.hip, zstd_dfast_ragged_hip.hip) and
-// decode_hip.hip (by zstd_ragged_split_hip.hip).  The other codecs' shared device code is in headers.
-#ifdef LZH_DEVICE_FUNCTIONS_ONLY
-#define LZH_TU_VAR static
-#else
-#define LZH_TU_VAR
-#endif
-
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -23,10 +23,9 @@
 // or (compact) one with a slot that ends past its region, is not processed: the entropy kernel of block 0 writes
 // csizes[i] = 0 and no kernel touches a slot for it.
 // Scan and pack are the existing ones (lzh_launch_compact_scans, lzh_launch_pack_ragged / lzh_launch_pack_compact).
-// zstdc_dfast_hip.hip is included for its device functions alone (it includes zstdc_hip.hip the same way) and
-// compiled with its flags; nothing here changes the uniform kernels' code.
-#define LZH_DFAST_DEVICE_FUNCTIONS_ONLY 1
-#include "zstdc_dfast_hip.hip"
+// The device functions are those of zstdc_dfast.h (and through it of zstdc.h), compiled with the flags of
+// zstdc_dfast_hip.hip; nothing here changes the uniform kernels' code.
+#include "zstdc_dfast.h"
 #include "zstd_dfast_slots.h"
 
 // ---------------------------------------------------------------------------------- uniform slots

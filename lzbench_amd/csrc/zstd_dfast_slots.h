@@ -4,8 +4,8 @@
 // for the slot-size kernel, the compact kernels' area offsets, the sizing functions and the host mirror of the
 // placement (api.cpp).
 // Plain C++ on the host: the level-3 parameters come from zstd_dfast_parse.h, and the areas before the tables are
-// restated here (lzh_zdslot_layout) so that nothing of zstdc_hip.hip is needed; lzh_launch_zstd_dfast_ragged
-// refuses to launch where this copy and that file's layout_for disagree.
+// restated here (lzh_zdslot_layout) so that nothing of zstdc.h is needed; lzh_launch_zstd_dfast_ragged
+// refuses to launch where this copy and that header's layout_for disagree.
 #pragma once
 #include "ragged_slots.h"
 #include "zstd_dfast_parse.h"
@@ -23,7 +23,7 @@ LZH_HD uint64_t lzh_zdslot_stage_bytes(uint64_t n) {
 // words, the entropy body after the frame's 9 bytes), so its slot is that of a 1-byte chunk: the convention of 3c.
 LZH_HD zdf::DParams lzh_zdslot_params(uint64_t n) { return zdf::params_for(3, n ? n : 1); }
 
-// A chunk's scratch slot: the areas of zc::layout_for (zstdc_hip.hip) for the chunk's own block size -- 1024 bytes of
+// A chunk's scratch slot: the areas of zc::layout_for (zstdc.h) for the chunk's own block size -- 1024 bytes of
 // header and Huffman table, sequences, literals, the block attempt, one Huffman stream, each 256-aligned -- then at
 // tab_off the long table and right after it the short one, each of the chunk's own level-3 row.  stride: the slot.
 struct LzhZdLayout {

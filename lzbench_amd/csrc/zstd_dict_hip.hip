@@ -18,9 +18,8 @@
 //                                    (zstdd::decode_frame's DictT): an offset may reach dict_bytes before the chunk's
 //                                    first byte; such a sequence copies dictionary bytes, then output bytes.
 //
-// zstdc_hip.hip is included for its device functions alone, the decoder's are zstdd.h; neither's kernels change.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "zstdc_hip.hip"
+// The compressor's device functions are zstdc.h, the decoder's are zstdd.h; neither's kernels change.
+#include "zstdc.h"
 #include "zstdd.h"
 #include "zstd_dict_parse.h"
 

@@ -22,9 +22,8 @@
 // uniform-slot kernels get them as arguments computed for max_bytes.  Every buffer descriptor the bodies build is
 // therefore bounded by the chunk's own slot.  chunk_size (the batch's max_bytes) and lds_arg still select the
 // hash-table kind alone: speed, never bytes.
-// As in zstd_ragged_hip.hip, zstdc_hip.hip is included for its device functions alone and compiled with its flags.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "zstdc_hip.hip"
+// As in zstd_ragged_hip.hip, the device functions are those of zstdc.h, compiled with the flags of zstdc_hip.hip.
+#include "zstdc.h"
 #include "zstd_ragged_slots.h"
 
 // (ZstdSlot: ragged_slots.h)

@@ -9,15 +9,14 @@
 // the bytes that may be read from it (nf + 16 here), nf its size, chunk_size the batch's max_bytes.  The bodies
 // derive the frame's parameters from nf on the device, as they do for a uniform batch's tail chunk; max_bytes only
 // selects the hash-table kind (speed, never bytes), sizes the slots and bounds the number of block launches.
-// zstdc_hip.hip is included for its device functions alone (and compiled with its flags), so every function has
-// the one caller per code object that it has in its own file.  Nothing here changes the uniform kernels' code
+// The device functions are those of zstdc.h, compiled here with the flags of zstdc_hip.hip, so every function has
+// the one caller per code object that it has in that unit.  Nothing here changes the uniform kernels' code
 // (profiles/traffic*.json are keyed to their code hashes).
 //
 // Frame i's staging slot and scratch area are slot i of the batch's, each sized for max_bytes and reached through
 // buffer descriptors of that size or less.  A chunk whose device-side size passes max_bytes is not processed: no
 // kernel touches its slots, its compressed size is 0.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#include "zstdc_hip.hip"
+#include "zstdc.h"
 
 // one wave per chunk; block k of every chunk (a chunk of fewer blocks returns at once)
 extern "C" __global__ void __launch_bounds__(64)

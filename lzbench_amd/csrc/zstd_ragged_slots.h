@@ -4,8 +4,8 @@
 // bytes, not nchunks x (the slots of the largest chunk).  One copy of the arithmetic for the slot-size kernel,
 // the sizing function and the host mirror of the placement: the sizes here are what the two kernel bodies
 // (zstdc_match_body.inc, zstdc_entropy_body.inc) address for a frame of n bytes alone.
-// Include after zstdc_hip.hip: the sizes come from its params_for and layout_for (host + device).  api.cpp, which
-// cannot include that file, reaches the functions through the host wrappers of zstd_ragged_compact_hip.hip
+// Include after zstdc.h: the sizes come from its params_for and layout_for (host + device).  api.cpp, which
+// does not compile that header, reaches the functions through the host wrappers of zstd_ragged_compact_hip.hip
 // (launch.h).
 #pragma once
 #include "launch.h"

@@ -11,63 +11,13 @@
 //                                  compression on: everything after the match finder is shared by fast and
 //                                  double-fast (strategy < ZSTD_lazy), so the body is the fast levels' as it is;
 //                                  the one strategy-dependent constant, ZSTD_selectEncodingType's 10 - strategy,
-//                                  is LZH_ZSTD_STRATEGY below.
+//                                  is LZH_ZSTD_STRATEGY 2 of zstdc_dfast.h.
 //
-// The match finder walks position by position (zstd_dfast_parse.h); the wave shares each position's loads,
-// counts match lengths 256 bytes a round and copies literals 64..256 bytes a round (count_fwd, count_bwd,
-// lit_copy of zstdc_hip.hip).  The two tables (long: 4 << hashLog, short: 4 << chainLog bytes, up to 768 KiB a
-// frame) live in the frame's scratch after the fast levels' areas and are served from L2; they start zeroed per
-// frame and persist across its blocks.  A table store becomes visible to the wave's later loads through a wait
-// for it (GlbTab::fence) and loads that bypass L1, as in the fast levels' scratch table.
-//
-// zstdc_hip.hip is included for its device functions alone (and compiled with its flags); nothing here changes
-// the fast levels' kernels.
-#define LZH_DEVICE_FUNCTIONS_ONLY 1
-#define LZH_ZSTD_STRATEGY 2   // ZSTD_dfast: ZSTD_selectEncodingType's thresholds (the one place the stage reads it)
-#include "zstdc_hip.hip"
-#include "zstd_dfast_parse.h"
+// The uniform kernels, their launcher and the sizing function.  The device code -- the entropy stage of zstdc.h for
+// ZSTD_dfast, the parser and zdf::WaveEnv -- comes with zstdc_dfast.h, where the match finder is described; nothing
+// here changes the fast levels' kernels.
+#include "zstdc_dfast.h"
 
-namespace zdf {
-
-// the level-3 parameters in the shape the entropy body reads (window, block size, literal compression on)
-__host__ __device__ inline zc::ZParams entropy_params(int level, uint64_t n) {
-    const DParams D = params_for(level, n);
-    zc::ZParams p{};
-    p.ok = D.ok;
-    p.wlog = D.wlog;
-    p.hlog = D.hlog;
-    p.mls = D.mls;
-    p.step = 2;
-    p.bsize = D.bsize;
-    p.lit_off = 0;                      // double-fast never disables literal compression
-    return p;
-}
-
-// dfast_block's environment on one wave: uniform loads of the frame, the two tables in the frame's scratch
-struct WaveEnv {
-    const Bytes& in;
-    zc::GlbTab L, S;
-    zc::SeqOut& O;
-    int lane;
-    __device__ __forceinline__ uint32_t r32(int pos) const { return uni(in.w32(max(pos, 0))); }
-    __device__ __forceinline__ uint64_t r64(int pos) const { return uni64(zc::ld64(in, max(pos, 0))); }
-    __device__ __forceinline__ int count_fwd(int a, int b, int maxn) const { return zc::count_fwd(in, a, b, maxn, lane); }
-    __device__ __forceinline__ int count_bwd(int a, int b, int maxn) const { return zc::count_bwd(in, a, b, maxn, lane); }
-    __device__ __forceinline__ uint32_t long_get(uint32_t h) const { return uni(L.get(h)); }
-    __device__ __forceinline__ uint32_t short_get(uint32_t h) const { return uni(S.get(h)); }
-    __device__ __forceinline__ void long_put(uint32_t h, uint32_t v) const { if (lane == 0) L.put(h, v); }
-    __device__ __forceinline__ void short_put(uint32_t h, uint32_t v) const { if (lane == 0) S.put(h, v); }
-    __device__ __forceinline__ void fence() const { L.fence(); }
-    __device__ __forceinline__ void seq(int from, int ll, uint32_t offBase, uint32_t mlen) const {
-        zc::lit_copy(in, from, O.lits, O.nl, ll, lane);
-        O.nl += ll;
-        O.put(lane, (uint32_t)ll, offBase, mlen);
-    }
-};
-
-}  // namespace zdf
-
-#ifndef LZH_DFAST_DEVICE_FUNCTIONS_ONLY   // (zstd_dfast_ragged_hip.hip includes this file for the above and the kernel bodies alone)
 // one wave per frame; block k of every frame
 extern "C" __global__ void __launch_bounds__(64)
 lzh_zstd_dfast_match_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int level,
@@ -135,4 +85,3 @@ hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, u
     }
     return hipGetLastError();
 }
-#endif   // LZH_DFAST_DEVICE_FUNCTIONS_ONLY

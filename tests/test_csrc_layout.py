@@ -1,6 +1,7 @@
 """Layout of lzbench_amd/csrc: the decoders' shared device code is in headers (decode_win.h, zstdd.h), so is that of
-the LZ4 and snappy compressors (lz4c.h, snappyc.h), and the switches retired with the first move stay out.  Reads the
-sources only; the one compile is a syntax check of each compressor header on its own.
+the LZ4, snappy and zstd compressors (lz4c.h, snappyc.h, zstdc.h, zstdc_dfast.h), and the switches retired with the
+first move stay out.  Reads the sources only; the one compile is a syntax check of each compressor header on its own
+(and of the one include order that zstdc_dfast.h refuses).
 
 The ragged split decoder is the exception for now: zstd_ragged_split_hip.hip is the file it was, still includes
 decode_hip.hip under LZH_DEVICE_FUNCTIONS_ONLY and keeps its own LZH_ZSTD_MINW block; the split decoder's device code
@@ -51,10 +52,22 @@ def test_retired_switches_stay_out():
             assert name not in s, (f, name)
 
 
-# The LZ4 and snappy compressors: device code in lz4c.h and snappyc.h, which the codecs' own units and the ragged,
-# compact and dictionary units include.  (The zstd compressor, zstdc_hip.hip, is still included as text.)
-COMPRESS_HEADERS = ("lz4c.h", "snappyc.h")
+# The compressors: device code in lz4c.h, snappyc.h, zstdc.h and zstdc_dfast.h (the level-3 codec: zstdc.h compiled
+# for ZSTD_dfast, and namespace zdf), which the codecs' own units and the ragged, compact and dictionary units include.
+COMPRESS_HEADERS = ("lz4c.h", "snappyc.h", "zstdc.h", "zstdc_dfast.h")
 COMPRESS_UNITS = ("lz4c_hip.hip", "snappyc_hip.hip")
+ZSTDC_UNITS = ("zstdc_hip.hip", "zstdc_dfast_hip.hip")
+ZSTDC_CONSUMERS = ("zstd_ragged_hip.hip", "zstd_ragged_compact_hip.hip", "zstd_dict_hip.hip")   # (+ the dfast ragged unit)
+
+
+def _syntax_check(tmp_path, text):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc: cannot compile the header")
+    unit = tmp_path / "first.hip"
+    unit.write_text(text)
+    return subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", CSRC, str(unit)],
+                          capture_output=True, text=True)
 
 
 def test_no_unit_includes_the_lz4_or_snappy_compressor_file():
@@ -63,9 +76,53 @@ def test_no_unit_includes_the_lz4_or_snappy_compressor_file():
             assert not re.search(r'#\s*include\s*"%s"' % re.escape(unit), s), (f, unit)
 
 
+def test_no_unit_includes_a_zstd_compressor_file():
+    for f, s in _sources().items():
+        for unit in ZSTDC_UNITS:
+            assert not re.search(r'#\s*include\s*"%s"' % re.escape(unit), s), (f, unit)
+
+
+def test_include_modes_are_the_split_decoders_alone():
+    """LZH_DEVICE_FUNCTIONS_ONLY is left in decode_hip.hip and the one unit that includes it; the level-3 codec's
+    mode of its own is gone."""
+    src = _sources()
+    assert [f for f, s in src.items() if "LZH_DEVICE_FUNCTIONS_ONLY" in s.replace("LZH_DFAST_DEVICE_FUNCTIONS_ONLY", "")] \
+        == ["decode_hip.hip", SPLIT_UNIT]
+    assert [f for f, s in src.items() if "LZH_DFAST_DEVICE_FUNCTIONS_ONLY" in s] == []
+
+
+def test_zstd_compress_units_include_the_headers():
+    src = _sources()
+    for f in ("zstdc_hip.hip",) + ZSTDC_CONSUMERS + ("zstdc_dfast.h",):
+        assert '#include "zstdc.h"' in src[f], f
+    for f in ("zstdc_dfast_hip.hip", "zstd_dfast_ragged_hip.hip"):
+        assert '#include "zstdc_dfast.h"' in src[f], f
+        assert '#include "zstdc.h"' not in src[f], f   # (through zstdc_dfast.h, which sets the strategy first)
+    for h in ("zstdc.h", "zstdc_dfast.h"):
+        assert "__global__" not in src[h], h
+        code = [l for l in src[h].splitlines() if l.strip() and not l.lstrip().startswith("//")]
+        assert code[0] == "#pragma once", h
+
+
+def test_only_zstdc_hip_makes_the_compressor_tables_external():
+    """LZH_TU_VAR, the LZH_HDR_VAR of the compressor's header: static in zstdc.h unless the unit defined it, and
+    zstdc_hip.hip alone defines it empty; common.h no longer knows of it."""
+    assert _defining("LZH_TU_VAR", empty=True) == ["zstdc_hip.hip"]
+    assert sorted(_defining("LZH_TU_VAR")) == ["zstdc.h", "zstdc_hip.hip"]
+    assert [f for f, s in _sources().items() if "LZH_TU_VAR" in s] == ["zstdc.h", "zstdc_hip.hip"]
+
+
+def test_zstdc_after_its_default_strategy_is_an_error(tmp_path):
+    """zstdc.h first and zstdc_dfast.h after it would compile the entropy stage for strategy 1 without a word."""
+    r = _syntax_check(tmp_path, '#include "zstdc.h"\n#include "zstdc_dfast.h"\n')
+    assert r.returncode != 0
+    assert "zstdc_dfast.h must come before zstdc.h" in r.stderr
+
+
 def test_compress_header_units_know_no_include_mode():
     src = _sources()
-    for f in COMPRESS_UNITS + ("ragged_hip.hip", "ragged_compact_hip.hip", "lz4_dict_hip.hip") + COMPRESS_HEADERS:
+    for f in COMPRESS_UNITS + ZSTDC_UNITS + ("ragged_hip.hip", "ragged_compact_hip.hip", "lz4_dict_hip.hip") \
+            + ZSTDC_CONSUMERS + ("zstd_dfast_ragged_hip.hip",) + COMPRESS_HEADERS:
         assert "LZH_DEVICE_FUNCTIONS_ONLY" not in src[f], f
     for f in ("lz4c_hip.hip", "ragged_hip.hip", "ragged_compact_hip.hip", "lz4_dict_hip.hip"):
         assert '#include "lz4c.h"' in src[f], f
@@ -74,7 +131,7 @@ def test_compress_header_units_know_no_include_mode():
 
 
 def test_makefile_names_no_compressor_file_as_a_prerequisite():
-    """The two files stand in the Makefile only as the sources of their own objects (the pattern rule)."""
+    """The four files stand in the Makefile only as the sources of their own objects (the pattern rule)."""
     text = re.sub(r"\\\n", " ", _sources()["Makefile"])
     for line in text.splitlines():
         if line.startswith(("#", "\t")) or ":" not in line:
@@ -82,17 +139,11 @@ def test_makefile_names_no_compressor_file_as_a_prerequisite():
         target, _, prereq = line.partition(":")
         if prereq.startswith("="):   # (a `:=` assignment)
             continue
-        for unit in COMPRESS_UNITS:
+        for unit in COMPRESS_UNITS + ZSTDC_UNITS:
             assert unit not in prereq.split(), line
 
 
 @pytest.mark.parametrize("header", COMPRESS_HEADERS)
 def test_compress_header_compiles_when_included_first(header, tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc: cannot compile the header")
-    unit = tmp_path / "first.hip"
-    unit.write_text('#include "%s"\n' % header)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", CSRC, str(unit)],
-                       capture_output=True, text=True)
+    r = _syntax_check(tmp_path, '#include "%s"\n' % header)
     assert r.returncode == 0, r.stderr

@@ -88,7 +88,7 @@ def test_skewed_batch_sizes_to_a_fraction_of_the_uniform_slots():
 
 
 # ---- the host mirror against the regions --------------------------------------------------------------------------
-# The per-frame scratch of the two zstd kernels, restated from csrc/zstdc_hip.hip (params_for: the clevels.h rows
+# The per-frame scratch of the two zstd kernels, restated from csrc/zstdc.h (params_for: the clevels.h rows
 # for sizes up to 16 KiB / 128 KiB / 256 KiB / above, levels <= 0 | 1 | 2 as (windowLog, hashLog); layout_for).
 ROWS = {3: [(14, 13), (14, 15), (14, 15)], 2: [(17, 12), (17, 13), (17, 15)], 1: [(18, 13), (18, 14), (18, 16)],
         0: [(19, 13), (19, 14), (20, 16)]}

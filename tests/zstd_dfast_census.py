@@ -7,8 +7,8 @@ zstdc_dfast_match_body.inc does.  The counters live in that environment and in t
 header is untouched.  Because the walk is shared with the kernel it is anchored to the reference and not to itself by
 tests/test_zstd_dfast_census.py (block by block against the reference build's frame, sequence by sequence against
 ZSTD_generateSequences).  Lines are zstd 1.5.2's lib/compress/zstd_double_fast.c unless another file is named; the
-kernel side is lzbench_amd/csrc/zstdc_dfast_hip.hip (WaveEnv) with count_fwd / count_bwd / lit_copy / GlbTab of
-zstdc_hip.hip.
+kernel side is lzbench_amd/csrc/zstdc_dfast.h (WaveEnv) with count_fwd / count_bwd / lit_copy / GlbTab of
+zstdc.h.
 
   params/row/n>262144, n<=262144, n<=131072, n<=16384   the clevels.h row of level 3 (table sizes, mls)
   params/mls4, mls5            minMatch of the row: hash_short over 4 or 5 bytes
