@@ -532,8 +532,8 @@ int lzh_debug_zstd_dict_params(int level, size_t n, size_t dict_bytes, uint32_t*
 long lzh_debug_zstd_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
                                uint32_t* seqs, size_t cap);
 
-/* Debug only, host arithmetic only (they may change; no decode call takes this layout yet, so the split decoder runs
- * with the uniform-slot temp above alone and there is no public sizing function): a compact layout of the split
+/* Debug only, host arithmetic only (they may change; the call that decodes through this layout and its sizing
+ * function are section 3g below): a compact layout of the split
  * decoder's temp, in which every frame's area is laid out for that frame's own decoded size and placed by an
  * exclusive scan, and the Huffman job list is sized for the sum of the frames' own block slots, so temp grows with the
  * batch's total bytes plus a constant per chunk, not with nchunks x (the area of max_chunk_bytes).  A frame of n
@@ -566,6 +566,40 @@ int lzh_debug_zstd_ragged_split_compact_slots(const uint64_t* out_sizes, size_t 
                                               uint8_t* in_split);
 int lzh_debug_zstd_ragged_split_compact_layout(size_t total_out_bytes, size_t max_chunk_bytes, size_t nchunks,
                                                uint64_t* out);
+
+/* ---- 3g. ragged zstd batches: the split decoder with temp sized by the batch's total bytes ---------------- */
+/* lzh_zstd_decompress_ragged_async (3c) through the four-kernel split decoder in the compact temp layout described
+ * above: every frame's area laid out for the frame's own decoded size and placed on the device by an exclusive scan,
+ * the Huffman job list sized for the sum of the frames' own block slots.  A batch of one 16 MiB chunk among 4,095 of
+ * 4 KiB decodes in the split decoder with 145,583,104 bytes of temp, where 3c's split temp is 142,105,035,776.
+ * lzh_zstd_ragged_decompress_split_compact_temp_bytes: host arithmetic, exactly out[22] of
+ * lzh_debug_zstd_ragged_split_compact_layout for the same arguments, and 0 where that call returns LZH_EARG
+ * (max_chunk_bytes below 16384 or above 16 MiB): non-decreasing in each argument, never above
+ * lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, nchunks) plus the four per-chunk arrays.
+ * lzh_zstd_decompress_ragged_split_compact_async: the contract of lzh_zstd_decompress_ragged_async, word for word --
+ * per-chunk pointers and sizes of any alignment; d_offsets may be NULL (derived into temp); raw-stored chunks are
+ * copied; a chunk over max_chunk_bytes is not processed (d_status[i] = -1, nothing of its frame read, nothing of its
+ * output or temp written); nchunks == 0 returns LZH_OK and launches nothing; all checks before any device call, in
+ * this order: max_chunk_bytes over 16 MiB -> LZH_EARG, nchunks == 0, null pointers -> LZH_EARG, temp_bytes below
+ * lzh_zstd_ragged_decompress_temp_bytes -> LZH_ESPACE; every launch on hip_stream, no side stream, event, host
+ * synchronisation or size read back -- with one addition: total_out_bytes, the caller's host-side upper bound of the
+ * sum of d_out_bytes[i] over the chunks not larger than max_chunk_bytes (the promise the compact compress calls take).
+ * The decoder is chosen by temp_bytes as in 3c: with at least the compact sizing answer (where that is not 0) the
+ * split decoder runs in the compact layout; with less, every frame decodes in the one-wave decoder.  Statuses and
+ * bytes are the same either way, and the same as lzh_zstd_decompress_ragged_async's with either of its temps.
+ * Placement: a frame of d_out_bytes[i] = n takes the area and the job slots of a frame of n bytes (above; a chunk over
+ * max_chunk_bytes 0 of each), both placed by exclusive scans into regions 7 .. 10 of the layout;
+ * lzh_debug_zstd_ragged_split_compact_slots is the host mirror, bit for bit.  A frame within max_chunk_bytes whose area
+ * or job slots end outside their regions -- possible only in a batch that breaks the promise -- is not refused: it
+ * decodes in the one-wave decoder, so a broken promise costs speed and never a result, and nothing is written outside
+ * d_temp[0 .. temp_bytes).  So does a frame of more blocks than ceil(n / 128 KiB) + 1 (its own block slots).
+ * The debug hooks lzh_debug_zstd_legacy, lzh_debug_zstd_huf_sections and lzh_debug_zstd_hufpar act as on 3c's call. */
+size_t lzh_zstd_ragged_decompress_split_compact_temp_bytes(size_t total_out_bytes, size_t max_chunk_bytes,
+                                                           size_t nchunks);
+int lzh_zstd_decompress_ragged_split_compact_async(const void* d_packed, size_t packed_readable,
+        const uint32_t* d_csizes, const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+        size_t nchunks, size_t max_chunk_bytes, size_t total_out_bytes, int32_t* d_status,
+        void* d_temp, size_t temp_bytes, void* hip_stream);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

@@ -110,6 +110,8 @@ SIGNATURES = {
     "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
     "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
+    "lzh_zstd_ragged_decompress_split_compact_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "lzh_zstd_decompress_ragged_split_compact_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_ragged_split_compact_slots": (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_ragged_split_compact_layout": (C.c_int, [_SZ, _SZ, _SZ, _P]),
     "lzh_zstd_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
@@ -435,6 +437,11 @@ class RaggedCodec:
     (lzh_zstd_ragged_decompress_split_temp_bytes: about 280 KiB per chunk at 128 KiB, several times faster on large
     batches); where there is none (max_chunk_bytes below 16 KiB) the temp stays the small one and every frame
     decodes in the one-wave kernel, as with split_decode=False.
+    compact_decode=True (zstd with split_decode=True and no dictionary, else ValueError) runs that decoder in the
+    compact temp layout of include/lzbench_hip.h 3g: the temp is sized from max_total_bytes
+    (lzh_zstd_ragged_decompress_split_compact_temp_bytes: about twice the batch plus 18 KiB per chunk), so a batch
+    of one large chunk among many small ones can use the split decoder; decompress passes max_total_bytes as the
+    promised total, and where the sizing call answers 0 the temp stays the small one.
     dictionary=<uint8 tensor of 8 .. 65536 bytes> (lz4 / lz4fast without compact, else ValueError; chunks up to
     4 MiB) shares one LZ4 dictionary among all chunks (include/lzbench_hip.h 3d): compress() writes what
     LZ4_loadDict + LZ4_compress_fast_continue write for each chunk, decompress() is LZ4_decompress_safe_usingDict.
@@ -450,7 +457,7 @@ class RaggedCodec:
 
     def __init__(self, codec: str, max_chunk_bytes: int, max_chunks: int, level: int = 0, device=None,
                  max_total_bytes: Optional[int] = None, compact: bool = False, split_decode: bool = False,
-                 compact_scratch: bool = False, dictionary=None):
+                 compact_scratch: bool = False, dictionary=None, compact_decode: bool = False):
         import torch
         self.torch = torch
         self.codec = CODECS[codec]
@@ -470,6 +477,13 @@ class RaggedCodec:
         if split_decode and not self.zstd:
             raise ValueError("ragged batches: split_decode is a zstd option")
         self.split_decode = split_decode
+        if compact_decode and not self.zstd:
+            raise ValueError("ragged batches: compact_decode is a zstd option")
+        if compact_decode and not split_decode:
+            raise ValueError("ragged batches: compact_decode is a layout of the split decoder (pass split_decode=True)")
+        if compact_decode and dictionary is not None:
+            raise ValueError("ragged batches: a zstd dictionary goes with the one-wave decoder (no compact_decode)")
+        self.compact_decode = compact_decode
         zdict = dictionary is not None and codec in ("zstd", "zstd_fast")
         if zdict and (compact_scratch or split_decode):
             raise ValueError("ragged batches: a zstd dictionary goes with the uniform-slot layout and the one-wave decoder "
@@ -512,6 +526,10 @@ class RaggedCodec:
             dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
             if split_decode:   # (0: no split decoder for chunks of this size)
                 dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
+            if compact_decode:   # (3g: the promised total after max_chunk_bytes; sized from it, 0 as above)
+                self._decompress = L.lzh_zstd_decompress_ragged_split_compact_async
+                dt = (L.lzh_zstd_ragged_decompress_split_compact_temp_bytes(self.max_total, max_chunk_bytes, max_chunks)
+                      or L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks))
         elif dictionary is not None:   # (3d: the dictionary's own calls; it is kept with 16 readable bytes after it)
             nd = int(dictionary.numel())
             ct = L.lzh_lz4_dict_compress_temp_bytes(nd, max_chunk_bytes, max_chunks)
@@ -598,8 +616,8 @@ class RaggedCodec:
         self.k = k
         rc = self._decompress(*self._dhead, packed.data_ptr(), packed.numel(), csizes.data_ptr(),
                               offsets.data_ptr() if offsets is not None else None, d[0].data_ptr(), d[1].data_ptr(), k,
-                              self.max_chunk_bytes, self.status.data_ptr(), self.dtemp.data_ptr(), self.dtemp.numel(),
-                              self._stream())
+                              self.max_chunk_bytes, *((self.max_total,) if self.compact_decode else ()),
+                              self.status.data_ptr(), self.dtemp.data_ptr(), self.dtemp.numel(), self._stream())
         if rc:
             raise RuntimeError(f"{self._decompress.__name__} failed ({rc})")
 

@@ -678,7 +678,7 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
         });
 }
 
-// ---- 3c, compact layout of the split decoder's temp, debug calls only (no decode call uses it yet): every frame's
+// ---- 3c, compact layout of the split decoder's temp, the debug calls (3g below decodes through it): every frame's
 // area laid out for its own size and placed by a scan (zstd_split_slots.h); zstd_ragged_split_compact_temp lays the
 // temp out ----
 int lzh_debug_zstd_ragged_split_compact_layout(size_t total_out_bytes, size_t max_chunk_bytes, size_t nchunks,
@@ -714,6 +714,40 @@ int lzh_debug_zstd_ragged_split_compact_slots(const uint64_t* out_sizes, size_t 
         jo += sz.jobs;
     }
     return LZH_OK;
+}
+
+// ---- 3g. the ragged split decoder in that layout: zstd_ragged_split_compact_temp is the sizing answer and what
+// the launch is handed; 3c's contract, with the promised total.  Below the compact answer (or where there is none)
+// every frame decodes in the one-wave kernel ----
+size_t lzh_zstd_ragged_decompress_split_compact_temp_bytes(size_t total_out_bytes, size_t max_chunk_bytes,
+                                                           size_t nchunks) {
+    return zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks).total;
+}
+
+int lzh_zstd_decompress_ragged_split_compact_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                                   const uint64_t* d_offsets, void* const* d_out_ptrs,
+                                                   const uint64_t* d_out_bytes, size_t nchunks, size_t max_chunk_bytes,
+                                                   size_t total_out_bytes, int32_t* d_status, void* d_temp,
+                                                   size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return ragged_decompress(
+        max_chunk_bytes <= kLz4SplitMax, nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
+        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+            const ZstdRaggedSplitCompactTemp z = zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks);
+            uint8_t* base = (uint8_t*)d_temp;
+            if (z.ok && temp_bytes >= z.total) {
+                const LzhZstdSplitCompactTemp T = {
+                    base + z.areas, base + z.dummy, (int32_t*)(base + z.state), base + z.fields,
+                    (uint32_t*)(base + z.njobs), base + z.jobs,
+                    {(uint32_t*)(base + z.area_sz), (uint32_t*)(base + z.job_cnt), (uint64_t*)(base + z.area_off),
+                     (uint64_t*)(base + z.job_off), z.reg.areas, z.reg.jobs}};
+                return lzh_launch_zstd_decompress_ragged_split_compact((const uint8_t*)d_packed, packed_readable, offs,
+                                                                       d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes,
+                                                                       d_status, (uint32_t)nchunks, T, s);
+            }
+            return lzh_launch_zstd_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
+                                                     d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, s);
+        });
 }
 
 // ---- 3b, compact compress layout: every chunk's slots sized from its own size (ragged_slots.h); compact_temp

@@ -77,12 +77,29 @@ hipError_t lzh_launch_zstd_decompress_ragged_split(const uint8_t* packed, uint64
                                                    void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
                                                    int32_t* status, uint32_t nchunks, const LzhZstdSplitTemp& split,
                                                    hipStream_t s);
-// the compact temp layout of the split decoder (zstd_split_slots.h derives it; host arithmetic for api.cpp's debug
-// calls, no launcher yet): the two regions that hold every batch of at most nchunks frames of at most max_bytes that
+// the compact temp layout of the split decoder (zstd_split_slots.h derives it; host arithmetic for api.cpp's sizing
+// and debug calls): the two regions that hold every batch of at most nchunks frames of at most max_bytes that
 // sums to at most total bytes, and the {area bytes, Huffman job slots} of a frame of n bytes
 struct LzhZsplitRegions { uint64_t areas, jobs; };   // (bytes; Huffman jobs)
 LzhZsplitRegions lzh_zstd_split_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks);
 LzhZsplitRegions lzh_zstd_split_compact_slot(uint64_t n);
+// the split decoder through that layout (zstd_ragged_split_compact_hip.hip; include/lzbench_hip.h 3g).  T: the regions of
+// ZstdRaggedSplitCompactTemp (temp_layout.h); `slots` is the compress side's layout struct (below) carrying the
+// placement -- stage_sz / stage_off / stage_cap: the area sizes, their scan, the area region's bytes; rec_sz / rec_off /
+// rec_cap: the job counts, their scan, the job list's slots.  The call fills the four arrays, sets the frame states
+// (a chunk over max_bytes: kDone, status -1; a frame that ends outside a region: kLegacy) and runs the split kernels
+// and the one-wave kernel, every launch on s; with lzh_debug_zstd_legacy(1) it is lzh_launch_zstd_decompress_ragged.
+struct LzhCompactLayout;
+struct LzhZstdSplitCompactTemp;
+hipError_t lzh_launch_zstd_decompress_ragged_sel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                                                 const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
+                                                 uint64_t max_bytes, int32_t* status, uint32_t nchunks,
+                                                 const int32_t* zsel, hipStream_t s);
+hipError_t lzh_launch_zstd_decompress_ragged_split_compact(const uint8_t* packed, uint64_t packed_readable,
+                                                           const uint64_t* offsets, const uint32_t* csizes,
+                                                           void* const* out_ptrs, const uint64_t* out_bytes,
+                                                           uint64_t max_bytes, int32_t* status, uint32_t nchunks,
+                                                           const LzhZstdSplitCompactTemp& T, hipStream_t s);
 // decode_hip.hip, for the ragged launcher and its layout: the sizes of the split decoder's temp for nchunks frames of
 // up to `chunk` bytes (a frame's area, the dummy words, a frame's fields, a frame's Huffman jobs); the test hooks
 // lzh_debug_zstd_legacy / _hufpar and the Huffman sections a wave (4 or 8: the hook, else by nchunks and the device's
@@ -168,6 +185,15 @@ struct LzhCompactLayout {
     uint64_t* stage_off;
     uint64_t* rec_off;
     uint64_t stage_cap, rec_cap;
+};
+struct LzhZstdSplitCompactTemp {
+    uint8_t* areas;      // the area region
+    uint8_t* dummy;      // the sequence waves' dummy words
+    int32_t* state;      // nchunks frame states
+    void* zfr;           // nchunks frame fields
+    uint32_t* njobs;     // the Huffman jobs' counter
+    void* jobs;          // slots.rec_cap Huffman jobs
+    LzhCompactLayout slots;
 };
 hipError_t lzh_launch_compact_scans(const LzhCompactLayout& L, uint32_t nchunks, hipStream_t s);
 hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,

@@ -283,7 +283,7 @@ static inline ZstdRaggedSplitTemp zstd_ragged_split_temp(size_t nchunks, size_t 
     return t;
 }
 
-// ---- the same with the compact layout (zstd_split_slots.h; the debug calls of api.cpp, no decode call yet): every
+// ---- the same with the compact layout (zstd_split_slots.h; 3g's decode call and the debug calls of api.cpp): every
 // frame's area laid out for the frame's own size and placed by a scan, the job list sized for the frames' own block
 // slots.  The regions of zstd_ragged_split_temp
 // in its order -- the area region and the job list sized by lzh_zstd_split_compact_regions for the promised total,

@@ -28,6 +28,15 @@ struct RaggedOut {
     __device__ __forceinline__ uint64_t frames() const { return nchunks; }
     __device__ __forceinline__ uint8_t* at(uint64_t frame) const { return (uint8_t*)ptrs[frame]; }
     __device__ __forceinline__ uint8_t* idle() const { return nullptr; }
+    // (the temp side: uniform slots, as UniformOut's)
+    __device__ __forceinline__ ZLayout layout() const { return zlayout(slot()); }
+    __device__ __forceinline__ const uint8_t* area(const uint8_t* zt, uint32_t frame, const ZLayout& Z) const {
+        return zt + (uint64_t)frame * Z.stride;
+    }
+    __device__ __forceinline__ uint64_t tables(uint32_t frame, uint32_t fmin, const ZLayout& Z) const {
+        return (uint64_t)(frame - fmin) * Z.stride + Z.hufs();
+    }
+    __device__ __forceinline__ uint8_t* dummy(uint8_t* zt, uint64_t nfr, const ZLayout& Z) const { return zt + nfr * Z.stride; }
 };
 // zstdd_hufpar_body.inc names the output of frame jf `out + (uint64_t)jf * chunk_size` and lays the temp out with
 // zlayout(chunk_size).  Here `out` is the batch's pointer array and `chunk_size` a RaggedSlotBytes: an integer times
@@ -43,6 +52,9 @@ __device__ __forceinline__ RaggedFrame operator*(uint64_t frame, RaggedSlotBytes
 __device__ __forceinline__ uint8_t* operator+(RaggedPtrs p, RaggedFrame f) { return (uint8_t*)p.ptrs[f.index]; }
 }  // namespace zsplit
 
+// (zstd_ragged_split_compact_hip.hip includes this file up to here, for decode_hip.hip's device functions and the
+// geometry above: the kernels and launchers below are this unit's alone)
+#ifndef LZH_ZSPLIT_GEOMETRY_ONLY
 // The header and execution kernels run the uniform kernels' bodies under the names those use: chunk's output is
 // out + ooff with ooff = 0, its size min(chunk_size, n_total - ooff) with n_total the chunk's own size and
 // chunk_size = max_bytes, for which the per-frame temp is laid out.
@@ -141,7 +153,7 @@ lzh_zstd_decompress_ragged_sel_kernel(const uint8_t* packed, uint64_t packed_rea
 
 // the area arithmetic of the compact temp layout (zstd_split_slots.h) for api.cpp, which cannot include
 // decode_hip.hip, where the layout it derives from (zsplit::zlayout) lives: the two regions, and the area and job
-// slots of a frame of n bytes.  Host arithmetic only; no kernel decodes through that layout yet.
+// slots of a frame of n bytes.  Host arithmetic; zstd_ragged_split_compact_hip.hip decodes through that layout.
 LzhZsplitRegions lzh_zstd_split_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks) {
     return lzh_zsplit_regions(total, max_bytes, nchunks);
 }
@@ -189,3 +201,14 @@ hipError_t lzh_launch_zstd_decompress_ragged_split(const uint8_t* packed, uint64
                        offsets, csizes, out_ptrs, out_bytes, max_bytes, status, (const int32_t*)zst);
     return hipGetLastError();
 }
+
+// the one-wave kernel over the frames at kLegacy alone (zsel: the frame states), for the compact layout's launcher
+hipError_t lzh_launch_zstd_decompress_ragged_sel(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                                                 const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
+                                                 uint64_t max_bytes, int32_t* status, uint32_t nchunks,
+                                                 const int32_t* zsel, hipStream_t s) {
+    hipLaunchKernelGGL(lzh_zstd_decompress_ragged_sel_kernel, dim3(nchunks), dim3(64), 0, s, packed, packed_readable,
+                       offsets, csizes, out_ptrs, out_bytes, max_bytes, status, zsel);
+    return hipGetLastError();
+}
+#endif   // LZH_ZSPLIT_GEOMETRY_ONLY

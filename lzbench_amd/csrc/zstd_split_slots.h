@@ -1,5 +1,5 @@
 // lzbench_amd/csrc/zstd_split_slots.h -- area arithmetic of the compact layout of the ragged zstd split decoder
-// (the debug calls of include/lzbench_hip.h 3c; no decode call uses it yet): every frame's temp area is laid out
+// (include/lzbench_hip.h 3g, zstd_ragged_split_compact_hip.hip, and the debug calls of 3c): every frame's temp area is laid out
 // for the frame's own decoded size and placed by an exclusive scan, and the Huffman job list holds the sum of the
 // frames' own block slots, so temp grows with the batch's total bytes, not nchunks x (the area of the largest
 // chunk).  One copy of the arithmetic, host and device: the sizes here are what the four kernel bodies address for

@@ -2,6 +2,8 @@
 // decode_hip.hip; lzh_zstd_exec_ragged_kernel, zstd_ragged_split_hip.hip) for a frame the header and literal
 // kernels left at kGo.  The including kernel has: win (its LDS), lane, chunk, out + ooff, n_total, chunk_size (as in
 // zstdd_hdr_body.inc), packed, packed_readable, offsets, csizes, status, zt, zst, zfr.
+// A third consumer, lzh_zstd_exec_compact_kernel (zstd_ragged_split_compact_hip.hip), passes the frame's own size as
+// chunk_size and a zsplit::Placed as zt: as in zstdd_hdr_body.inc, keep the area `zt + chunk * Z.stride`.
 // Textual, not a function: see zstdd_hdr_body.inc.
     const int sv = zfr[chunk].sv;                                // then the sequence kernel's
     if (sv != zsplit::kGo) {

@@ -4,6 +4,9 @@
 // zst / zfr), out + ooff (the frame's output address), min(chunk_size, n_total - ooff) (its size), chunk_size (the
 // largest frame of the launch: the per-frame temp is laid out for it), packed, packed_readable, offsets, csizes,
 // status, zt, zst, zfr, stats, jobs, njobs.
+// A third consumer, lzh_zstd_hdr_compact_kernel (zstd_ragged_split_compact_hip.hip), passes the frame's own size as
+// chunk_size and a zsplit::Placed as zt, whose operator+ drops what is added: the body must keep naming the frame's
+// area `zt + chunk * Z.stride`, zt first and one sum, or that kernel addresses another frame's area.
 // Textual, not a function: the uniform kernel's code must stay bit-identical (profiles are keyed to kernel code
 // hashes).
     const int part = (int)min(chunk_size, n_total - ooff);

@@ -3,6 +3,10 @@
 // including kernel has: out + (uint64_t)jf * chunk_size (the output address of frame jf, which the body reads from
 // the job), chunk_size (converts to the largest frame of the launch: the per-frame temp is laid out for it), packed,
 // packed_readable, offsets, status, zt, zst, jobs, njobs, par.
+// A third consumer, lzh_zstd_hufpar_compact_kernel (zstd_ragged_split_compact_hip.hip), passes a zsplit::CompactBytes
+// as chunk_size (a layout of stride 1 and no blocks) and a zsplit::HufTables as zt, whose operator+ takes the frame's
+// index: the body must keep naming the table slots `zt + (uint64_t)jf * Z.stride + Z.hufs()` in that order, and use
+// Z for nothing else, or that kernel reads another frame's tables.
 // Textual, not a function: see zstdd_hdr_body.inc.
     using namespace zsplit;
     using namespace zstdd;
