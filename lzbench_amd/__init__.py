@@ -20,6 +20,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import ragged_calls
+
 __all__ = [
     "ExtensionMissing", "lib", "CODECS", "COMP_DESC", "CompressorDesc", "find_compressor",
     "compress_chunks", "decompress_chunks", "chunk_sizes_for", "datagen", "DeviceCodec", "RaggedCodec",
@@ -98,44 +100,17 @@ SIGNATURES = {
     "lzh_debug_gather_order": (C.c_int, [_SZ, _P, _P, _P]),
     "lzh_compress_async": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_decompress_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
-    "lzh_ragged_decompress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
     "lzh_ragged_max_packed_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
-    "lzh_compress_ragged_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_decompress_ragged_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
-    "lzh_zstd_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
-    "lzh_zstd_ragged_decompress_temp_bytes": (_SZ, [_SZ, _SZ]),
     "lzh_zstd_ragged_max_packed_bytes": (_SZ, [_SZ, _SZ]),
-    "lzh_zstd_ragged_decompress_split_temp_bytes": (_SZ, [_SZ, _SZ]),
     "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
-    "lzh_zstd_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_zstd_decompress_ragged_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
-    "lzh_zstd_ragged_decompress_split_compact_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
-    "lzh_zstd_decompress_ragged_split_compact_async": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_ragged_split_compact_slots": (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_ragged_split_compact_layout": (C.c_int, [_SZ, _SZ, _SZ, _P]),
-    "lzh_zstd_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
-    "lzh_zstd_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
-    "lzh_zstd_dfast_ragged_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
-    "lzh_zstd_dfast_compress_ragged_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_zstd_dfast_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
-    "lzh_zstd_dfast_compress_ragged_compact_async": (C.c_int, [C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_dfast_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_dfast_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
-    "lzh_ragged_compact_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
-    "lzh_compress_ragged_compact_async": (C.c_int, [C.c_int, C.c_int, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_debug_ragged_compact_slots": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_ragged_compact_regions": (C.c_int, [C.c_int, _SZ, _SZ, _SZ, _P]),
-    "lzh_lz4_dict_compress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
-    "lzh_lz4_dict_decompress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
-    "lzh_lz4_compress_ragged_dict_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_lz4_decompress_ragged_dict_async": (C.c_int, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
-    "lzh_zstd_dict_compress_temp_bytes": (_SZ, [C.c_int, _SZ, _SZ, _SZ]),
-    "lzh_zstd_dict_decompress_temp_bytes": (_SZ, [_SZ, _SZ, _SZ]),
-    "lzh_zstd_compress_ragged_dict_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _SZ, _P]),
-    "lzh_zstd_decompress_ragged_dict_async": (C.c_int, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _P]),
     "lzh_debug_zstd_dict_params": (C.c_int, [C.c_int, _SZ, _SZ, _P]),
     "lzh_debug_zstd_dict_parse": (C.c_long, [C.c_int, _P, _SZ, _P, _SZ, _P, _SZ]),
     "lzh_compress_kernel_only": (C.c_int, [C.c_int, C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
@@ -143,6 +118,8 @@ SIGNATURES = {
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
     "lzh_datagen": (_SZ, [C.c_int, C.c_uint64, _P, _SZ]),
     "lzh_version": (C.c_char_p, []),
+    # the ragged async calls of 3b .. 3g and their *_temp_bytes functions: generated from the table
+    **ragged_calls.signatures(),
 }
 
 
@@ -491,70 +468,36 @@ class RaggedCodec:
         if dictionary is not None and not zdict and (codec != "lz4" and codec != "lz4fast" or compact):
             raise ValueError("ragged batches: a dictionary goes with codec lz4 / lz4fast / zstd / zstd_fast and the "
                              "uniform-slot layout (compact=False)")
-        # the variant, chosen once: the compress and decompress calls (their names go into the error texts), each with
-        # the arguments it takes before the chunk arrays, and the sizing call; the compact layouts take the batch's
-        # total too (sizing: after the codec or level; compress: after max_chunk_bytes, and max_total as it is then:
-        # a caller may lower its promise between calls)
-        self._promise = compact or compact_scratch
-        if zdict:   # (3f: the zstd dictionary's own calls; the tensor is kept with 16 readable bytes after it)
-            nd = int(dictionary.numel())
-            ct = L.lzh_zstd_dict_compress_temp_bytes(self.level, nd, max_chunk_bytes, max_chunks)
-            dt = L.lzh_zstd_dict_decompress_temp_bytes(nd, max_chunk_bytes, max_chunks)
-            if ct == 0 or dt == 0:
+        # the variant, chosen once: a compress and a decompress row of ragged_calls.RAGGED_CALLS (zstd_dfast decodes with
+        # zstd's), and the values their heads and sizing calls pick from by name
+        family = ("zstd_dict" if zdict else "zstd_dfast" if dfast else "zstd" if self.zstd
+                  else "lz4_dict" if dictionary is not None else "lz")
+        self._crec = ragged_calls.COMPRESS[family, compact or compact_scratch]
+        self._drec = ragged_calls.DECOMPRESS["zstd" if dfast else family, compact_decode]
+        self._head = dict(codec=self.codec, level=self.level)
+        if dictionary is not None:
+            nd = self._head["dict_bytes"] = int(dictionary.numel())
+        sized = dict(self._head, total=self.max_total, max_chunk_bytes=max_chunk_bytes, nchunks=max_chunks)
+        ct = self._crec.temp_bytes(L, **sized)
+        dt = self._drec.temp_bytes(L, roomy=split_decode, **sized)
+        if ct == 0 or dt == 0:
+            if zdict:
                 raise ValueError(f"ragged batches: zstd level {self.level} (1, -1 .. -5) / a dictionary of {nd} bytes "
                                  f"(8 .. 131072) / chunks of {max_chunk_bytes} bytes (up to 131072) are not supported")
-            flat = dictionary.reshape(-1)
-            if bytes(flat[:4].cpu().numpy().tobytes()) == b"\x37\xa4\x30\xec":   # (read once, here)
-                raise ValueError("ragged batches: the dictionary begins with zstd's dictionary magic; trained "
-                                 "dictionaries are not supported (the bytes would be used as content)")
-            dev = device or torch.device("cuda", torch.cuda.current_device())
-            self.dictionary = torch.zeros(nd + 16, dtype=torch.uint8, device=dev)
-            self.dictionary[:nd].copy_(flat)
-            self._compress, self._decompress = L.lzh_zstd_compress_ragged_dict_async, L.lzh_zstd_decompress_ragged_dict_async
-            self._chead, self._dhead = (self.level, self.dictionary.data_ptr(), nd), (self.dictionary.data_ptr(), nd)
-            sizing = None
-        elif self.zstd:
-            if dfast:
-                self._compress = (L.lzh_zstd_dfast_compress_ragged_compact_async if compact_scratch
-                                  else L.lzh_zstd_dfast_compress_ragged_async)
-                sizing = (L.lzh_zstd_dfast_ragged_compact_compress_temp_bytes if compact_scratch
-                          else L.lzh_zstd_dfast_ragged_compress_temp_bytes)
-            else:
-                self._compress = L.lzh_zstd_compress_ragged_compact_async if compact_scratch else L.lzh_zstd_compress_ragged_async
-                sizing = L.lzh_zstd_ragged_compact_compress_temp_bytes if compact_scratch else L.lzh_zstd_ragged_compress_temp_bytes
-            self._chead, self._decompress, self._dhead = (self.level,), L.lzh_zstd_decompress_ragged_async, ()
-            dt = L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks)
-            if split_decode:   # (0: no split decoder for chunks of this size)
-                dt = L.lzh_zstd_ragged_decompress_split_temp_bytes(max_chunk_bytes, max_chunks) or dt
-            if compact_decode:   # (3g: the promised total after max_chunk_bytes; sized from it, 0 as above)
-                self._decompress = L.lzh_zstd_decompress_ragged_split_compact_async
-                dt = (L.lzh_zstd_ragged_decompress_split_compact_temp_bytes(self.max_total, max_chunk_bytes, max_chunks)
-                      or L.lzh_zstd_ragged_decompress_temp_bytes(max_chunk_bytes, max_chunks))
-        elif dictionary is not None:   # (3d: the dictionary's own calls; it is kept with 16 readable bytes after it)
-            nd = int(dictionary.numel())
-            ct = L.lzh_lz4_dict_compress_temp_bytes(nd, max_chunk_bytes, max_chunks)
-            dt = L.lzh_lz4_dict_decompress_temp_bytes(nd, max_chunk_bytes, max_chunks)
-            if ct == 0 or dt == 0:
+            if dictionary is not None:
                 raise ValueError(f"ragged batches: a dictionary of {nd} bytes (8 .. 65536) / chunks of {max_chunk_bytes} "
                                  "bytes (up to 4 MiB) are not supported")
-            dev = device or torch.device("cuda", torch.cuda.current_device())
-            self.dictionary = torch.zeros(nd + 16, dtype=torch.uint8, device=dev)
-            self.dictionary[:nd].copy_(dictionary.reshape(-1))
-            self._compress, self._decompress = L.lzh_lz4_compress_ragged_dict_async, L.lzh_lz4_decompress_ragged_dict_async
-            self._chead, self._dhead = (self.level, self.dictionary.data_ptr(), nd), (self.dictionary.data_ptr(), nd)
-            sizing = None
-        else:
-            self._compress = L.lzh_compress_ragged_compact_async if compact else L.lzh_compress_ragged_async
-            sizing = L.lzh_ragged_compact_compress_temp_bytes if compact else L.lzh_ragged_compress_temp_bytes
-            self._chead, self._decompress, self._dhead = (self.codec, self.level), L.lzh_decompress_ragged_async, (self.codec,)
-            dt = L.lzh_ragged_decompress_temp_bytes(self.codec, max_chunk_bytes, max_chunks)
-        if sizing is not None:
-            ct = sizing(self._chead[0], *((self.max_total,) if self._promise else ()), max_chunk_bytes, max_chunks)
-        if ct == 0 or dt == 0:
             raise ValueError(f"ragged batches: codec {codec} (level {self.level}) / chunks of {max_chunk_bytes} bytes "
                              "are not supported")
+        if zdict and bytes(dictionary.reshape(-1)[:4].cpu().numpy().tobytes()) == b"\x37\xa4\x30\xec":   # (read once, here)
+            raise ValueError("ragged batches: the dictionary begins with zstd's dictionary magic; trained "
+                             "dictionaries are not supported (the bytes would be used as content)")
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
         u8 = dict(dtype=torch.uint8, device=self.dev)
+        if dictionary is not None:   # (3d, 3f: the calls read the dictionary with 16 readable bytes after it)
+            self.dictionary = torch.zeros(nd + 16, **u8)
+            self.dictionary[:nd].copy_(dictionary.reshape(-1))
+            self._head["dict"] = self.dictionary.data_ptr()
         if self.zstd:
             self.max_packed = L.lzh_zstd_ragged_max_packed_bytes(self.max_total, max_chunks)
         else:
@@ -594,11 +537,17 @@ class RaggedCodec:
         copy, so the call can be captured in a graph."""
         self._in = d   # (kept alive until the next call: the kernels read it asynchronously)
         self.k = k
-        rc = self._compress(*self._chead, d[0].data_ptr(), d[1].data_ptr(), k, self.max_chunk_bytes,
-                            *((self.max_total,) if self._promise else ()), self.packed.data_ptr(), self.packed.numel(), self.csizes.data_ptr(), self.offsets.data_ptr(),
-                            self.ctemp.data_ptr(), self.ctemp.numel(), self._stream())
+        self._call(self._crec, in_ptrs=d[0].data_ptr(), in_bytes=d[1].data_ptr(), packed=self.packed.data_ptr(),
+                   packed_cap=self.packed.numel(), csizes=self.csizes.data_ptr(), offsets=self.offsets.data_ptr(),
+                   temp=self.ctemp.data_ptr(), temp_bytes=self.ctemp.numel())
+
+    def _call(self, rec, **buffers) -> None:
+        """rec on the current stream: its head, the batch's shape (the promised total as max_total is now: a caller
+        may lower its promise between calls) and the buffers, each argument picked by name."""
+        rc = rec(lib(), **self._head, nchunks=self.k, max_chunk_bytes=self.max_chunk_bytes, total=self.max_total,
+                 stream=self._stream(), **buffers)
         if rc:
-            raise RuntimeError(f"{self._compress.__name__} failed ({rc})")
+            raise RuntimeError(f"{rec.symbol} failed ({rc})")
 
     def decompress(self, out_buf, out_offsets, out_sizes, packed=None, csizes=None, offsets=None) -> None:
         """Decode chunk i to out_buf[out_offsets[i] : out_offsets[i] + out_sizes[i]]; self.status[i] = its
@@ -614,12 +563,10 @@ class RaggedCodec:
         csizes = self.csizes if csizes is None else csizes
         self._out = d
         self.k = k
-        rc = self._decompress(*self._dhead, packed.data_ptr(), packed.numel(), csizes.data_ptr(),
-                              offsets.data_ptr() if offsets is not None else None, d[0].data_ptr(), d[1].data_ptr(), k,
-                              self.max_chunk_bytes, *((self.max_total,) if self.compact_decode else ()),
-                              self.status.data_ptr(), self.dtemp.data_ptr(), self.dtemp.numel(), self._stream())
-        if rc:
-            raise RuntimeError(f"{self._decompress.__name__} failed ({rc})")
+        self._call(self._drec, packed=packed.data_ptr(), packed_readable=packed.numel(), csizes=csizes.data_ptr(),
+                   offsets=offsets.data_ptr() if offsets is not None else None, out_ptrs=d[0].data_ptr(),
+                   out_bytes=d[1].data_ptr(), status=self.status.data_ptr(), temp=self.dtemp.data_ptr(),
+                   temp_bytes=self.dtemp.numel())
 
     def packed_total(self) -> int:
         return int(self.offsets[self.k].item())

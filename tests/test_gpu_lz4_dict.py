@@ -58,8 +58,7 @@ def codec(torch, d: np.ndarray, maxb, k, acc=1, residue=0):
         assert rc.dictionary.data_ptr() % 4 == 0
         rc.dict_shifted = torch.zeros(len(d) + residue + 16, dtype=torch.uint8, device="cuda")
         rc.dict_shifted[residue: residue + len(d)].copy_(torch.from_numpy(d))
-        p = rc.dict_shifted.data_ptr() + residue
-        rc._chead, rc._dhead = (rc.level, p, len(d)), (p, len(d))
+        rc._head["dict"] = rc.dict_shifted.data_ptr() + residue
     return rc
 
 

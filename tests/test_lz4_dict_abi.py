@@ -1,8 +1,7 @@
-"""CPU: the C-ABI of the LZ4 dictionary calls (include/lzbench_hip.h 3d) -- the sizing functions and the argument
-checks, all made before any device call (null device pointers reach them), and RaggedCodec's argument errors."""
+"""CPU: the C-ABI of the LZ4 dictionary calls (include/lzbench_hip.h 3d) -- the sizing functions and RaggedCodec's
+argument errors (the async calls' argument checks: tests/test_ragged_calls_abi.py)."""
 import itertools
 
-import numpy as np
 import pytest
 
 import lzbench_amd as L
@@ -49,41 +48,6 @@ def test_sizing_is_monotone_and_within_the_bound(lib):
         plain = lib.lzh_ragged_compress_temp_bytes(L.LZH_CODEC_LZ4, m, k)
         assert plain > 0
         assert lib.lzh_lz4_dict_compress_temp_bytes(nd, m, k) <= plain + 65536 + 64 * k, (nd, m, k)
-
-
-def _compress(lib, level=1, dict_p=1, nd=4096, ptrs=1, nchunks=4, maxb=4096, temp=1, temp_bytes=None):
-    need = lib.lzh_lz4_dict_compress_temp_bytes(nd, maxb, nchunks)
-    tb = need if temp_bytes is None else temp_bytes
-    # (non-null pointers are the address 1: every check that sees them comes before any device call)
-    return lib.lzh_lz4_compress_ragged_dict_async(level, dict_p or None, nd, ptrs or None, ptrs or None, nchunks, maxb,
-                                                  ptrs or None, 1 << 20, ptrs or None, ptrs or None, temp or None, tb, None)
-
-
-def _decompress(lib, dict_p=1, nd=4096, ptrs=1, nchunks=4, maxb=4096, temp=1, temp_bytes=None, offsets=1):
-    need = lib.lzh_lz4_dict_decompress_temp_bytes(nd, maxb, nchunks)
-    tb = need if temp_bytes is None else temp_bytes
-    return lib.lzh_lz4_decompress_ragged_dict_async(dict_p or None, nd, ptrs or None, 1 << 20, ptrs or None, offsets or None,
-                                                    ptrs or None, ptrs or None, nchunks, maxb, ptrs or None, temp or None,
-                                                    tb, None)
-
-
-@pytest.mark.parametrize("call", [_compress, _decompress], ids=["compress", "decompress"])
-def test_refusals_and_their_order(lib, call):
-    # arguments first: with null pointers and no temp they still answer LZH_EARG for the argument
-    for nd in (0, 7, 65537):
-        assert call(lib, nd=nd) == LZH_EARG and call(lib, nd=nd, nchunks=0) == LZH_EARG
-    assert call(lib, maxb=4 * MIB + 1) == LZH_EARG and call(lib, maxb=4 * MIB + 1, nchunks=0) == LZH_EARG
-    # nchunks == 0: LZH_OK, whatever the pointers and the temp
-    assert call(lib, nchunks=0, ptrs=0, dict_p=0, temp=0, temp_bytes=0) == LZH_OK
-    # null pointers before the temp size
-    assert call(lib, ptrs=0, temp_bytes=0) == LZH_EARG
-    assert call(lib, dict_p=0, temp_bytes=0) == LZH_EARG
-    assert call(lib, temp=0, temp_bytes=0) == LZH_EARG
-    # then the temp size: one byte below the sizing answer
-    f = lib.lzh_lz4_dict_compress_temp_bytes if call is _compress else lib.lzh_lz4_dict_decompress_temp_bytes
-    assert call(lib, temp_bytes=f(4096, 4096, 4) - 1) == LZH_ESPACE
-    assert call(lib, nd=8, maxb=4 * MIB, temp_bytes=f(8, 4 * MIB, 4) - 1) == LZH_ESPACE
-    assert call(lib, nd=65536, maxb=0, temp_bytes=f(65536, 0, 4) - 1) == LZH_ESPACE
 
 
 def test_ragged_codec_argument_errors():

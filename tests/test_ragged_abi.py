@@ -1,6 +1,5 @@
-"""CPU: the ragged-batch calls of include/lzbench_hip.h 3b without a device -- sizing functions, argument
-checks (all made before any HIP call), and the invariance of the uniform kernels' code hashes."""
-import ctypes as C
+"""CPU: the ragged-batch calls of include/lzbench_hip.h 3b without a device -- sizing functions (the calls'
+argument checks: tests/test_ragged_calls_abi.py), and the invariance of the uniform kernels' code hashes."""
 import os
 import shutil
 import subprocess
@@ -12,17 +11,6 @@ from lzbench_amd.kernel_hash import kernel_hashes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LZ4, SNAPPY = L.LZH_CODEC_LZ4, L.LZH_CODEC_SNAPPY
-OK, EARG, ESPACE = 0, -1, -3
-FAKE = 0x1000   # a non-null "device pointer": the checks under test return before anything reads it
-
-
-def _compress(lib, codec, nchunks, maxb, temp, ptrs=FAKE, sizes=FAKE, packed=FAKE, cs=FAKE, offs=FAKE, tp=FAKE):
-    return lib.lzh_compress_ragged_async(codec, 1, ptrs, sizes, nchunks, maxb, packed, 1 << 20, cs, offs, tp, temp, None)
-
-
-def _decompress(lib, codec, nchunks, maxb, temp, packed=FAKE, cs=FAKE, ptrs=FAKE, sizes=FAKE, st=FAKE, tp=FAKE):
-    return lib.lzh_decompress_ragged_async(codec, packed, 1 << 20, cs, None, ptrs, sizes, nchunks, maxb, st, tp, temp,
-                                           None)
 
 
 @pytest.mark.parametrize("codec", [LZ4, SNAPPY])
@@ -57,28 +45,6 @@ def test_sizing_functions(codec):
     for maxb in (0, 13, 65536, 200000, 16 << 20):
         for k in (1, 3, 1000):
             assert lib.lzh_ragged_compress_temp_bytes(codec, maxb, k) >= k * lib.lzh_stage_stride(codec, maxb)
-
-
-def test_argument_checks_without_a_device():
-    lib = L.lib()
-    for codec in (L.LZH_CODEC_MEMCPY, L.LZH_CODEC_ZSTD, L.LZH_CODEC_LZ4F, L.LZH_CODEC_NVLZ4):
-        assert _compress(lib, codec, 4, 65536, 1 << 30) == EARG
-        assert _decompress(lib, codec, 4, 65536, 1 << 30) == EARG
-        assert _compress(lib, codec, 0, 65536, 0, 0, 0, 0, 0, 0, 0) == EARG
-    for codec in (LZ4, SNAPPY):
-        big = (16 << 20) + 1
-        assert _compress(lib, codec, 4, big, 1 << 40) == EARG
-        assert _decompress(lib, codec, 4, big, 1 << 40) == EARG
-        ct = lib.lzh_ragged_compress_temp_bytes(codec, 65536, 4)
-        dt = lib.lzh_ragged_decompress_temp_bytes(codec, 65536, 4)
-        for null in ("ptrs", "sizes", "packed", "cs", "offs"):
-            assert _compress(lib, codec, 4, 65536, ct, **{null: None}) == EARG, null
-        for null in ("packed", "cs", "ptrs", "sizes", "st"):
-            assert _decompress(lib, codec, 4, 65536, dt, **{null: None}) == EARG, null
-        assert _compress(lib, codec, 4, 65536, ct - 1) == ESPACE
-        assert _decompress(lib, codec, 4, 65536, dt - 1) == ESPACE
-        assert _compress(lib, codec, 0, 65536, 0, None, None, None, None, None, None) == OK
-        assert _decompress(lib, codec, 0, 65536, 0, None, None, None, None, None, None) == OK
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
-"""CPU: the ragged zstd level-3 calls of include/lzbench_hip.h 3e without a device -- the sizing functions, the
-argument checks (all made before any HIP call) and the host mirror of the compact slot placement against the slot
+"""CPU: the ragged zstd level-3 calls of include/lzbench_hip.h 3e without a device -- the sizing functions (the
+calls' argument checks: tests/test_ragged_calls_abi.py) and the host mirror of the compact slot placement against the slot
 arithmetic recomputed here from the level-3 rows of clevels.h."""
 import ctypes as C
 import json
@@ -11,7 +11,7 @@ import pytest
 import lzbench_amd as L
 
 ZSTD = L.LZH_CODEC_ZSTD
-OK, EARG, ESPACE = 0, -1, -3
+OK, EARG = 0, -1
 FAKE = 0x1000   # a non-null "device pointer": the checks under test return before anything reads it
 MAX = 16 << 20
 SIZES = [0, 1, 6, 7, 63, 64, 65, 255, 1024, 4099, 16384, 16385, 65536, 131072, 131073, 200000, 262144, 262145, 300000,
@@ -76,18 +76,6 @@ def cmp_size(lib, total, maxb, k, level=3):
     return lib.lzh_zstd_dfast_ragged_compact_compress_temp_bytes(level, total, maxb, k)
 
 
-def uni_call(lib, level, k, maxb, temp, ptrs=FAKE, sizes=FAKE, packed=FAKE, cs=FAKE, offs=FAKE, tp=FAKE):
-    return lib.lzh_zstd_dfast_compress_ragged_async(level, ptrs, sizes, k, maxb, packed, 1 << 20, cs, offs, tp, temp, None)
-
-
-def cmp_call(lib, level, k, maxb, total, temp, ptrs=FAKE, sizes=FAKE, packed=FAKE, cs=FAKE, offs=FAKE, tp=FAKE):
-    return lib.lzh_zstd_dfast_compress_ragged_compact_async(level, ptrs, sizes, k, maxb, total, packed, 1 << 20, cs, offs,
-                                                            tp, temp, None)
-
-
-NULLS = (None,) * 6
-
-
 @pytest.mark.parametrize("level,maxb", [(1, 65536), (2, 65536), (4, 65536), (-1, 65536), (0, 4096), (19, 4096),
                                         (3, MAX + 1), (1, MAX + 1)])
 def test_sizing_is_zero_exactly_where_the_call_refuses(lib, level, maxb):
@@ -95,10 +83,6 @@ def test_sizing_is_zero_exactly_where_the_call_refuses(lib, level, maxb):
     one = (C.c_uint64 * 1)(5)
     flag = (C.c_uint8 * 1)()
     assert uni_size(lib, maxb, 4, level) == 0 and cmp_size(lib, 4 * 4096, maxb, 4, level) == 0
-    assert uni_call(lib, level, 4, maxb, 1 << 40) == EARG
-    assert cmp_call(lib, level, 4, maxb, 4 * 4096, 1 << 40) == EARG
-    assert uni_call(lib, level, 0, maxb, 0, *NULLS) == EARG            # (before the empty batch)
-    assert cmp_call(lib, level, 0, maxb, 0, 0, *NULLS) == EARG
     assert lib.lzh_debug_zstd_dfast_ragged_compact_regions(level, 4 * 4096, maxb, 4, out) == EARG
     assert lib.lzh_debug_zstd_dfast_ragged_compact_slots(level, one, 1, maxb, 5, out, out, flag) == EARG
 
@@ -155,23 +139,6 @@ def test_compact_answer_is_within_the_uniform_slot_answer(lib):
                 assert cmp_size(lib, t, maxb, k) <= uni_size(lib, maxb, k) + arrays_bytes(k), (t, maxb, k)
     # the skewed batch of the GPU test: below a tenth of the uniform-slot temp
     assert 10 * cmp_size(lib, 255 * 4096 + (1 << 20), 1 << 20, 256) < uni_size(lib, 1 << 20, 256)
-
-
-@pytest.mark.parametrize("maxb", [65536, 300000, 0])
-def test_check_order(lib, maxb):
-    k = 4
-    ut, ct = uni_size(lib, maxb, k), cmp_size(lib, k * maxb, maxb, k)
-    assert ut > 0 and ct > 0
-    for null in ("ptrs", "sizes", "packed", "cs", "offs", "tp"):
-        for temp in (1 << 40, 0):                                       # (null pointers before temp_bytes)
-            assert uni_call(lib, 3, k, maxb, temp, **{null: None}) == EARG, null
-            assert cmp_call(lib, 3, k, maxb, k * maxb, temp, **{null: None}) == EARG, null
-        assert uni_call(lib, 1, k, maxb, 0, **{null: None}) == EARG    # (the level first of all)
-    assert uni_call(lib, 3, k, maxb, ut - 1) == ESPACE
-    assert cmp_call(lib, 3, k, maxb, k * maxb, ct - 1) == ESPACE
-    assert uni_call(lib, 3, 0, maxb, 0, *NULLS) == OK                   # (nchunks == 0 before the null pointers)
-    assert cmp_call(lib, 3, 0, maxb, 0, 0, *NULLS) == OK
-    assert uni_call(lib, 3, 1 << 31, maxb, 0) == EARG                   # (the launch grid before temp_bytes)
 
 
 def mirror(lib, sizes, maxb, total):

@@ -1,33 +1,22 @@
-"""CPU: sizing, argument checks and the Python refusals of the zstd dictionary calls (include/lzbench_hip.h 3f).
-Every check of the async calls comes before any device call, so they run here with made-up pointers."""
+"""CPU: sizing and the Python refusals of the zstd dictionary calls (include/lzbench_hip.h 3f; the order of the async
+calls' argument checks: tests/test_ragged_calls_abi.py)."""
 import ctypes as C
 
 import pytest
 
 import lzbench_amd as L
+from ragged_fake import fake_call
 
 LZH_OK, LZH_EARG, LZH_ESPACE = 0, -1, -3
 LEVELS_OK, LEVELS_BAD = (1, -1, -2, -3, -4, -5), (0, 2, 3, 4, -6, 19)
 DICTS_OK, DICTS_BAD = (8, 9, 4096, 112640, 131072), (0, 7, 131073, 1 << 20)
 CHUNKS_OK, CHUNKS_BAD = (0, 1, 1000, 65536, 131072), (131073, 1 << 20)
-P = 0x10000   # a non-null pointer nobody dereferences
+COMPRESS, DECOMPRESS = "lzh_zstd_compress_ragged_dict_async", "lzh_zstd_decompress_ragged_dict_async"
 
 
 @pytest.fixture(scope="module")
 def lib():
     return L.lib()
-
-
-def _compress(lib, level=1, dict_p=P, nd=4096, ptrs=P, sizes=P, k=4, maxb=4096, packed=P, cs=P, offs=P, temp=P,
-              temp_bytes=1 << 40):
-    return lib.lzh_zstd_compress_ragged_dict_async(level, dict_p, nd, ptrs, sizes, k, maxb, packed, 1 << 30, cs, offs, temp,
-                                                   temp_bytes, None)
-
-
-def _decompress(lib, level=1, dict_p=P, nd=4096, ptrs=P, sizes=P, k=4, maxb=4096, packed=P, cs=P, offs=P, temp=P,
-                temp_bytes=1 << 40):
-    return lib.lzh_zstd_decompress_ragged_dict_async(dict_p, nd, packed, 1 << 30, cs, offs, ptrs, sizes, k, maxb, P, temp,
-                                                     temp_bytes, None)
 
 
 def test_sizing_is_zero_exactly_where_the_calls_refuse(lib):
@@ -40,9 +29,10 @@ def test_sizing_is_zero_exactly_where_the_calls_refuse(lib):
                 dt = lib.lzh_zstd_dict_decompress_temp_bytes(nd, maxb, 4)
                 assert (ct > 0) == ok and (dt > 0) == sizes_ok, (level, nd, maxb)
                 # (nchunks == 0 comes after the argument check)
-                assert _compress(lib, level=level, nd=nd, maxb=maxb, k=0) == (LZH_OK if ok else LZH_EARG)
-                assert _decompress(lib, nd=nd, maxb=maxb, k=0) == (LZH_OK if sizes_ok else LZH_EARG)
-                assert _compress(lib, level=level, nd=nd, maxb=maxb, temp_bytes=0) == (LZH_ESPACE if ok else LZH_EARG)
+                v = dict(level=level, dict_bytes=nd, max_chunk_bytes=maxb, temp_bytes=1 << 40)
+                assert fake_call(COMPRESS, nchunks=0, **v) == (LZH_OK if ok else LZH_EARG)
+                assert fake_call(DECOMPRESS, nchunks=0, **v) == (LZH_OK if sizes_ok else LZH_EARG)
+                assert fake_call(COMPRESS, nchunks=4, **dict(v, temp_bytes=0)) == (LZH_ESPACE if ok else LZH_EARG)
 
 
 def test_sizing_is_monotone(lib):
@@ -57,27 +47,6 @@ def test_sizing_is_monotone(lib):
     for level in LEVELS_OK:
         assert lib.lzh_zstd_dict_compress_temp_bytes(level, 65536, 1024, 4096) == \
                lib.lzh_zstd_dict_compress_temp_bytes(1, 65536, 1024, 4096)
-
-
-@pytest.mark.parametrize("call", [_compress, _decompress])
-def test_check_order(lib, call):
-    # arguments first, even with null pointers and no temp
-    assert call(lib, nd=7, dict_p=0, temp_bytes=0) == LZH_EARG
-    assert call(lib, maxb=131073, k=0) == LZH_EARG
-    # nchunks == 0 before the pointers
-    assert call(lib, k=0, dict_p=0, ptrs=0, temp=0, temp_bytes=0) == LZH_OK
-    # null pointers (the dictionary among them) before the temp size
-    for kw in (dict(dict_p=0), dict(ptrs=0), dict(sizes=0), dict(packed=0), dict(cs=0), dict(temp=0)):
-        assert call(lib, temp_bytes=0, **kw) == LZH_EARG, kw
-    if call is _compress:
-        assert call(lib, offs=0, temp_bytes=0) == LZH_EARG
-        assert call(lib, level=2) == LZH_EARG and call(lib, level=3) == LZH_EARG
-    # then the temp size: one byte below the sizing answer
-    f = (lambda nd, maxb, k: lib.lzh_zstd_dict_compress_temp_bytes(1, nd, maxb, k)) if call is _compress \
-        else lib.lzh_zstd_dict_decompress_temp_bytes
-    assert call(lib, temp_bytes=f(4096, 4096, 4) - 1) == LZH_ESPACE
-    assert call(lib, nd=8, maxb=131072, temp_bytes=f(8, 131072, 4) - 1) == LZH_ESPACE
-    assert call(lib, nd=131072, maxb=0, temp_bytes=f(131072, 0, 4) - 1) == LZH_ESPACE
 
 
 def test_debug_calls_refuse_what_the_async_calls_refuse(lib):

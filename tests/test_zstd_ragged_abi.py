@@ -1,11 +1,11 @@
-"""CPU: the ragged zstd calls of include/lzbench_hip.h 3c without a device -- sizing functions and argument
-checks (all made before any HIP call), and that the calls of 3b still refuse zstd."""
+"""CPU: the ragged zstd calls of include/lzbench_hip.h 3c without a device -- sizing functions, and that the
+calls of 3b still refuse zstd (the calls' own argument checks: tests/test_ragged_calls_abi.py)."""
 import pytest
 
 import lzbench_amd as L
 
 ZSTD = L.LZH_CODEC_ZSTD
-OK, EARG, ESPACE = 0, -1, -3
+EARG = -1
 FAKE = 0x1000   # a non-null "device pointer": the checks under test return before anything reads it
 MAX = 16 << 20
 # (level, largest max_chunk_bytes it is accepted for)
@@ -13,14 +13,6 @@ GOOD = [(1, MAX), (-1, MAX), (-5, MAX), (2, 131072)]
 # ZSTD_getParams size classes (16 KiB, 128 KiB, 256 KiB), block boundaries, the limit
 SIZES = [0, 1, 6, 7, 63, 64, 255, 1024, 4099, 16384, 16385, 65536, 131072, 131073, 200000, 262144, 262145, 300000,
          1 << 20, (1 << 20) + 1, MAX]
-
-
-def _compress(lib, level, nchunks, maxb, temp, ptrs=FAKE, sizes=FAKE, packed=FAKE, cs=FAKE, offs=FAKE, tp=FAKE):
-    return lib.lzh_zstd_compress_ragged_async(level, ptrs, sizes, nchunks, maxb, packed, 1 << 20, cs, offs, tp, temp, None)
-
-
-def _decompress(lib, nchunks, maxb, temp, packed=FAKE, cs=FAKE, ptrs=FAKE, sizes=FAKE, st=FAKE, tp=FAKE):
-    return lib.lzh_zstd_decompress_ragged_async(packed, 1 << 20, cs, None, ptrs, sizes, nchunks, maxb, st, tp, temp, None)
 
 
 @pytest.mark.parametrize("level,top", GOOD)
@@ -41,32 +33,10 @@ def test_sizing_is_nonzero_for_supported_levels(level, top):
 def test_unsupported_level_or_size(level, maxb):
     lib = L.lib()
     assert lib.lzh_zstd_ragged_compress_temp_bytes(level, maxb, 4) == 0
-    assert _compress(lib, level, 4, maxb, 1 << 40) == EARG
-    assert _compress(lib, level, 0, maxb, 0, None, None, None, None, None, None) == EARG   # (before the empty batch)
     if maxb > MAX:
         assert lib.lzh_zstd_ragged_decompress_temp_bytes(maxb, 4) == 0
-        assert _decompress(lib, 4, maxb, 1 << 40) == EARG
-        assert _decompress(lib, 0, maxb, 0, None, None, None, None, None, None) == EARG
     else:   # (the decoder has no level: any frame of lzbench's shape)
         assert lib.lzh_zstd_ragged_decompress_temp_bytes(maxb, 4) > 0
-
-
-@pytest.mark.parametrize("level,maxb", [(1, 65536), (-5, 300000), (2, 131072), (-1, 0)])
-def test_argument_checks_without_a_device(level, maxb):
-    lib = L.lib()
-    ct = lib.lzh_zstd_ragged_compress_temp_bytes(level, maxb, 4)
-    dt = lib.lzh_zstd_ragged_decompress_temp_bytes(maxb, 4)
-    assert ct > 0 and dt > 0
-    for null in ("ptrs", "sizes", "packed", "cs", "offs", "tp"):
-        assert _compress(lib, level, 4, maxb, ct, **{null: None}) == EARG, null
-        assert _compress(lib, level, 4, maxb, 0, **{null: None}) == EARG, null      # (null pointers before temp_bytes)
-    for null in ("packed", "cs", "ptrs", "sizes", "st", "tp"):
-        assert _decompress(lib, 4, maxb, dt, **{null: None}) == EARG, null
-        assert _decompress(lib, 4, maxb, 0, **{null: None}) == EARG, null
-    assert _compress(lib, level, 4, maxb, ct - 1) == ESPACE
-    assert _decompress(lib, 4, maxb, dt - 1) == ESPACE
-    assert _compress(lib, level, 0, maxb, 0, None, None, None, None, None, None) == OK
-    assert _decompress(lib, 0, maxb, 0, None, None, None, None, None, None) == OK
 
 
 @pytest.mark.parametrize("level,top", GOOD)

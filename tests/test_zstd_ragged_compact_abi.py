@@ -1,15 +1,13 @@
 """CPU: the compact compress layout of ragged zstd batches (include/lzbench_hip.h 3c) without a device -- the
 sizing function, the host mirror of the slot placement against the regions the sizing answer holds (the scratch
-slots against an independent restatement of the zstd kernels' per-frame layout), and the argument checks (all made
-before any HIP call)."""
+slots against an independent restatement of the zstd kernels' per-frame layout)."""
 import numpy as np
 import pytest
 
 import lzbench_amd as L
 
 ZSTD = L.LZH_CODEC_ZSTD
-OK, EARG, ESPACE = 0, -1, -3
-FAKE = 0x1000   # a non-null "device pointer": the checks under test return before anything reads it
+OK, EARG = 0, -1
 MAX = 16 << 20
 # (level, largest max_chunk_bytes it is accepted for)
 GOOD = [(1, MAX), (2, 131072), (-1, MAX), (-5, MAX)]
@@ -219,38 +217,16 @@ def test_a_broken_promise_drops_chunks_and_moves_none(level, top):
     assert pr.tolist() == [True, False, True] and so[1] == so[2] and co[1] == co[2]
 
 
-# ---- argument checks and their order ------------------------------------------------------------------------------
-def _compress(lib, level, nchunks, maxb, total, temp, ptrs=FAKE, sizes=FAKE, packed=FAKE, cs=FAKE, offs=FAKE, tp=FAKE):
-    return lib.lzh_zstd_compress_ragged_compact_async(level, ptrs, sizes, nchunks, maxb, total, packed, 1 << 20, cs,
-                                                      offs, tp, temp, None)
-
-
+# ---- the debug calls refuse what the async call refuses (its own checks: tests/test_ragged_calls_abi.py) -------------
 @pytest.mark.parametrize("level,maxb", [(0, 65536), (3, 65536), (2, 131073), (19, 4096), (1, MAX + 1), (-1, MAX + 1)])
 def test_unsupported_level_or_size_comes_first(level, maxb):
     lib = L.lib()
     one = np.zeros(1, np.uint64)
-    assert _compress(lib, level, 4, maxb, 1 << 18, 1 << 40) == EARG
-    assert _compress(lib, level, 0, maxb, 0, 0, None, None, None, None, None, None) == EARG   # (before the empty batch)
     assert lib.lzh_debug_zstd_ragged_compact_slots(level, one.ctypes.data, 1, maxb, 0, one.ctypes.data, one.ctypes.data,
                                                    one.ctypes.data) == EARG
     assert lib.lzh_debug_zstd_ragged_compact_regions(level, 0, maxb, 1, one.ctypes.data) == EARG
-
-
-@pytest.mark.parametrize("level,maxb", [(1, 65536), (-5, 300000), (2, 131072), (-1, 0)])
-def test_argument_checks_without_a_device(level, maxb):
-    lib = L.lib()
-    total = 2 * maxb + 17
-    ct = sizing(level, total, maxb, 4)
-    assert ct > 0
-    assert _compress(lib, level, 0, maxb, 0, 0, None, None, None, None, None, None) == OK     # (before the null pointers)
-    for null in ("ptrs", "sizes", "packed", "cs", "offs", "tp"):
-        assert _compress(lib, level, 4, maxb, total, ct, **{null: None}) == EARG, null
-        assert _compress(lib, level, 4, maxb, total, 0, **{null: None}) == EARG, null         # (before temp_bytes)
-    assert _compress(lib, level, 4, maxb, total, ct - 1) == ESPACE
-    assert _compress(lib, level, 1 << 31, maxb, total, 0) == EARG                             # launch grids, before temp
-    if maxb:
-        assert _compress(lib, level, 64, maxb, 64 * maxb, sizing(level, 8 * maxb, maxb, 64)) == ESPACE   # a larger promise
-    assert lib.lzh_debug_zstd_ragged_compact_regions(level, total, maxb, 4, None) == EARG
+    for lv, m in [(1, 65536), (-5, 300000), (2, 131072), (-1, 0)]:     # (a null output, at supported arguments)
+        assert lib.lzh_debug_zstd_ragged_compact_regions(lv, 2 * m + 17, m, 4, None) == EARG
 
 
 def test_python_value_errors():

@@ -1,13 +1,11 @@
-"""CPU: the sizing function and the argument checks of the ragged zstd split decoder's compact call
-(include/lzbench_hip.h 3g).  No device call is reached: every check runs before the first one."""
-import ctypes as C
-
+"""CPU: the sizing function of the ragged zstd split decoder's compact call (include/lzbench_hip.h 3g; the call's
+argument checks: tests/test_ragged_calls_abi.py)."""
 import numpy as np
 
 import lzbench_amd as L
 
 MIB = 1 << 20
-LZH_OK, LZH_EARG, LZH_ESPACE = 0, -1, -3          # (include/lzbench_hip.h)
+LZH_OK, LZH_EARG = 0, -1          # (include/lzbench_hip.h)
 
 
 def sizing(total, maxb, k):
@@ -59,27 +57,3 @@ def test_skewed_batch_sizing_is_arithmetic():
     compact = sizing(total, maxb, k)
     print("skewed batch: compact", compact, "uniform", uniform)
     assert 0 < compact * 10 < uniform
-
-
-def test_check_order_with_no_device():
-    lib = L.lib()
-    f = lib.lzh_zstd_decompress_ragged_split_compact_async
-    k, maxb, total = 4, 131072, 4 * 131072
-    small = lib.lzh_zstd_ragged_decompress_temp_bytes(maxb, k)
-    assert small > 0
-    p = C.c_void_p(0x1000)          # (never dereferenced: the calls below return before any device call)
-    good = dict(packed=p, csizes=p, offsets=p, out_ptrs=p, out_bytes=p, status=p, temp=p)
-
-    def call(nchunks=k, maxb=maxb, temp_bytes=small - 1, **kw):
-        a = dict(good, **kw)
-        return f(a["packed"], 1 << 20, a["csizes"], a["offsets"], a["out_ptrs"], a["out_bytes"], nchunks, maxb, total,
-                 a["status"], a["temp"], temp_bytes, None)
-
-    assert call(maxb=16 * MIB + 1) == LZH_EARG
-    assert call(maxb=16 * MIB + 1, nchunks=0) == LZH_EARG          # (the size check comes first)
-    none = {n: None for n in good}
-    assert call(nchunks=0, temp_bytes=0, **none) == LZH_OK
-    for name in ("packed", "csizes", "out_ptrs", "out_bytes", "status", "temp"):
-        assert call(**{name: None}) == LZH_EARG, name
-    assert call(temp_bytes=small - 1) == LZH_ESPACE
-    assert call(temp_bytes=small - 1, offsets=None) == LZH_ESPACE  # (d_offsets may be NULL: not an argument error)
