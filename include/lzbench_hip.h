@@ -489,8 +489,8 @@ int lzh_debug_zstd_dfast_ragged_compact_regions(int level, size_t total_in_bytes
  *       tables, and this call does not do that -- trained dictionaries are out of scope;
  *   max_chunk_bytes <= 131072, else LZH_EARG: dictionary plus chunk never pass 256 KiB, every frame has one block
  *       inside its window and the dictionary is never invalidated mid-frame;
- *   level: 1 and -1 .. -5, the levels whose row is ZSTD_fast in all four tables, else LZH_EARG (levels 2 and 3:
- *       double-fast with a dictionary is not built).
+ *   level: 1 and -1 .. -5, the levels whose row is ZSTD_fast in all four tables, else LZH_EARG (level 3,
+ *       double-fast with a dictionary, is the call of 3h; level 2 is not built).
  * The sizing functions return 0 exactly where the calls return LZH_EARG for those arguments; they are host arithmetic
  * and non-decreasing in dict_bytes, max_chunk_bytes and nchunks (and the same for every accepted level).  Check order:
  * arguments, nchunks == 0, null pointers (d_dict among them), then temp_bytes below the sizing answer: LZH_ESPACE; all
@@ -600,6 +600,49 @@ int lzh_zstd_decompress_ragged_split_compact_async(const void* d_packed, size_t 
         const uint32_t* d_csizes, const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
         size_t nchunks, size_t max_chunk_bytes, size_t total_out_bytes, int32_t* d_status,
         void* d_temp, size_t temp_bytes, void* hip_stream);
+
+/* ---- 3h. ragged zstd level-3 batches with a shared dictionary ------------------------------ */
+/* 3f's compress call at zstd's default level: what ZSTD_compress_usingDict(.., ZSTD_CLEVEL_DEFAULT) does for small
+ * records.  The contract is 3f's, word for word -- the dictionary arguments (one device buffer of any alignment, 16
+ * readable bytes after it, always used as content), per-chunk pointers and sizes, 16 readable bytes after every
+ * chunk, a chunk over max_chunk_bytes not processed (d_csizes[i] = 0, no slot touched), packed_cap enforced by the
+ * pack kernel, the raw-store rule, every launch on hip_stream with no side stream, event, host synchronisation or
+ * size read back -- with these differences:
+ *   level: 3 alone, else LZH_EARG (3f keeps refusing level 3, the calls of 3e keep having no dictionary);
+ *   limits: 8 <= dict_bytes <= 131072 and max_chunk_bytes <= 131072, else LZH_EARG;
+ *   check order: arguments, nchunks == 0 (LZH_OK, nothing launched), null pointers (d_dict among them), the launch
+ *       grid, then temp_bytes below the sizing answer: LZH_ESPACE; all before any device call.
+ * Compressed bytes: frame i is exactly what zstd 1.5.2 writes for ZSTD_compress_usingDict(fresh cctx, dst, cap,
+ * chunk i, n, dict, dict_bytes, 3) with the dictionary in a buffer of its own (not directly before the chunk):
+ * ZSTD_getParams_internal(3, n, dict_bytes) -- level 3's row by n + dict_bytes, adjusted for n + dict_bytes --
+ * ZSTD_fillDoubleHashTable(ZSTD_dtlm_fast) over the dictionary, ZSTD_compressBlock_doubleFast_extDict_generic, and the
+ * frame of 3e.  A chunk under 7 bytes gives the bytes of the plain call, an empty one the 9-byte frame.
+ * Decoding: lzh_zstd_decompress_ragged_dict_async of 3f, unchanged.
+ * lzh_zstd_dfast_dict_compress_temp_bytes: 0 exactly where the call returns LZH_EARG for those arguments; host
+ * arithmetic, non-decreasing in dict_bytes, max_chunk_bytes and nchunks.  Temp: nchunks staging slots of
+ * lzh_stage_stride(LZH_CODEC_ZSTD, max_chunk_bytes), nchunks scratch areas (the areas of 3c for a block of
+ * max_chunk_bytes and the frame's private pair of tables, (4 << hashLog) + (4 << chainLog) bytes, the largest any
+ * frame of such a batch can take: 512 KiB once dictionary plus chunk pass 32 KiB), and one filled pair of tables per
+ * (hashLog, chainLog, minMatch) class a batch can take, built once per call (a constant 1,309,952 bytes).
+ * The two debug calls are host arithmetic only: lzh_debug_zstd_dfast_dict_params writes windowLog, hashLog, chainLog,
+ * minMatch and the block size of ZSTD_getParams(3, n, dict_bytes) to out[0 .. 5); lzh_debug_zstd_dfast_dict_parse
+ * walks the parse on the host (host pointers, 16 readable bytes after each), writes the first cap sequences as
+ * (literal length, match length, offBase) triples and returns the count; where events is not null it adds to 14
+ * counters of the branches the walk reached, source in the dictionary / in the chunk: [0, 1] repcode at ip + 1,
+ * [2, 3] long match, [4, 5] short match kept, [6, 7] long match at ip + 1 taken, [8, 9] offset_2 loop iteration,
+ * [10] a forward count that crossed from the dictionary's end into the chunk's start, [11] a catch-up that stopped at
+ * the dictionary's first byte, [12] one that stopped at the chunk's first byte, [13] a repcode candidate refused by
+ * the three-byte overlap test.  LZH_EARG where the async call would return it (n taking max_chunk_bytes' place) or for
+ * a null pointer. */
+size_t lzh_zstd_dfast_dict_compress_temp_bytes(int level, size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks);
+int lzh_zstd_dfast_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes,
+                                              const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                              size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                                              void* hip_stream);
+int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out);
+long lzh_debug_zstd_dfast_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
+                                     uint32_t* seqs, size_t cap, uint64_t* events);
 
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */

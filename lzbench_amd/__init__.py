@@ -118,7 +118,9 @@ SIGNATURES = {
     "lzh_compress_finish_async": (C.c_int, [C.c_int, _P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ, _P, _P]),
     "lzh_datagen": (_SZ, [C.c_int, C.c_uint64, _P, _SZ]),
     "lzh_version": (C.c_char_p, []),
-    # the ragged async calls of 3b .. 3g and their *_temp_bytes functions: generated from the table
+    "lzh_debug_zstd_dfast_dict_params": (C.c_int, [C.c_int, _SZ, _SZ, _P]),
+    "lzh_debug_zstd_dfast_dict_parse": (C.c_long, [C.c_int, _P, _SZ, _P, _SZ, _P, _SZ, _P]),
+    # the ragged async calls of 3b .. 3h and their *_temp_bytes functions: generated from the table
     **ragged_calls.signatures(),
 }
 
@@ -429,6 +431,9 @@ class RaggedCodec:
     writes what ZSTD_compress_usingDict writes for each chunk with the dictionary in a buffer of its own, decompress()
     is ZSTD_decompress_usingDict.  A tensor that begins with zstd's dictionary magic (37 A4 30 EC) is refused with
     ValueError: the reference would read it as a trained dictionary, these calls use the bytes as content.
+    zstd_dfast_dict (a name of RaggedCodec's alone; level 3 and a dictionary, else ValueError) is level 3 with that
+    dictionary (include/lzbench_hip.h 3h): the limits, the refusals and the decoder of the paragraph above, compress()
+    writing what ZSTD_compress_usingDict writes at level 3.  zstd and zstd_dfast keep refusing level 3 with a dictionary.
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
@@ -437,15 +442,21 @@ class RaggedCodec:
                  compact_scratch: bool = False, dictionary=None, compact_decode: bool = False):
         import torch
         self.torch = torch
-        self.codec = CODECS[codec]
-        self.level = level if codec in _LEVELED else (1 if codec == "lz4" else 0)
+        # (zstd_dfast_dict, 3h: a name of RaggedCodec's alone -- level 3 with a dictionary; CODECS does not hold it)
+        dfdict = codec == "zstd_dfast_dict"
+        if dfdict and dictionary is None:
+            raise ValueError("ragged batches: zstd_dfast_dict needs a dictionary (without one: zstd_dfast)")
+        if dfdict and level != 3:
+            raise ValueError(f"ragged batches: zstd_dfast_dict is level 3 alone (level {level}; 1, -1 .. -5: zstd)")
+        self.codec = LZH_CODEC_ZSTD_DFAST if dfdict else CODECS[codec]
+        self.level = level if dfdict or codec in _LEVELED else (1 if codec == "lz4" else 0)
         self.max_chunk_bytes, self.max_chunks = max_chunk_bytes, max_chunks
         self.max_total = max_chunks * max_chunk_bytes if max_total_bytes is None else max_total_bytes
         L = lib()
         self.compact = compact
         # (zstd_dfast, level 3: the frames, the decoder, the options and the refusals of zstd; 3e's compress calls)
-        dfast = self.codec == LZH_CODEC_ZSTD_DFAST
-        self.zstd = self.codec == LZH_CODEC_ZSTD or dfast
+        dfast = self.codec == LZH_CODEC_ZSTD_DFAST and not dfdict
+        self.zstd = self.codec == LZH_CODEC_ZSTD or dfast or dfdict
         if self.zstd and compact:
             raise ValueError("ragged batches: compact=True is the LZ4 / snappy layout; for zstd pass compact_scratch=True")
         if compact_scratch and not self.zstd:
@@ -461,7 +472,7 @@ class RaggedCodec:
         if compact_decode and dictionary is not None:
             raise ValueError("ragged batches: a zstd dictionary goes with the one-wave decoder (no compact_decode)")
         self.compact_decode = compact_decode
-        zdict = dictionary is not None and codec in ("zstd", "zstd_fast")
+        zdict = dictionary is not None and codec in ("zstd", "zstd_fast", "zstd_dfast_dict")
         if zdict and (compact_scratch or split_decode):
             raise ValueError("ragged batches: a zstd dictionary goes with the uniform-slot layout and the one-wave decoder "
                              "(no compact_scratch, no split_decode)")
@@ -472,7 +483,8 @@ class RaggedCodec:
         # zstd's), and the values their heads and sizing calls pick from by name
         family = ("zstd_dict" if zdict else "zstd_dfast" if dfast else "zstd" if self.zstd
                   else "lz4_dict" if dictionary is not None else "lz")
-        self._crec = ragged_calls.COMPRESS[family, compact or compact_scratch]
+        # (3h compresses through its own call and decodes through 3f's)
+        self._crec = ragged_calls.COMPRESS["zstd_dfast_dict" if dfdict else family, compact or compact_scratch]
         self._drec = ragged_calls.DECOMPRESS["zstd" if dfast else family, compact_decode]
         self._head = dict(codec=self.codec, level=self.level)
         if dictionary is not None:
@@ -482,7 +494,7 @@ class RaggedCodec:
         dt = self._drec.temp_bytes(L, roomy=split_decode, **sized)
         if ct == 0 or dt == 0:
             if zdict:
-                raise ValueError(f"ragged batches: zstd level {self.level} (1, -1 .. -5) / a dictionary of {nd} bytes "
+                raise ValueError(f"ragged batches: zstd level {self.level} ({'3' if dfdict else '1, -1 .. -5'}) / a dictionary of {nd} bytes "
                                  f"(8 .. 131072) / chunks of {max_chunk_bytes} bytes (up to 131072) are not supported")
             if dictionary is not None:
                 raise ValueError(f"ragged batches: a dictionary of {nd} bytes (8 .. 65536) / chunks of {max_chunk_bytes} "

@@ -587,6 +587,53 @@ long lzh_debug_zstd_dict_parse(int level, const void* dict, size_t dict_bytes, c
     return lzh_zstd_dict_host_parse(level, (const uint8_t*)dict, dict_bytes, (const uint8_t*)src, n, seqs, cap);
 }
 
+// ---- 3h. ragged zstd level-3 batches with a shared dictionary: zstd_dfast_dict_temp, 3f's checks with level 3 alone,
+// the scan -> pack of 3c; the frames decode with 3f's call ----
+static bool zstd_dfast_dict_ok(int level, size_t dict_bytes, size_t max_chunk_bytes) {
+    return level == 3 && zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes);
+}
+
+size_t lzh_zstd_dfast_dict_compress_temp_bytes(int level, size_t dict_bytes, size_t max_chunk_bytes, size_t nchunks) {
+    return zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes)
+               ? zstd_dfast_dict_temp(dict_bytes, nchunks, max_chunk_bytes).total : 0;
+}
+
+int lzh_zstd_dfast_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes,
+                                              const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                              size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
+                                              uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                                              void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool ok = zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes);
+    const ZstdDictTemp t = ok ? zstd_dfast_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
+    const uint32_t k = (uint32_t)nchunks;
+    uint8_t* base = (uint8_t*)d_temp;
+    return ragged_compress(
+        ok, nchunks, d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total,
+        temp_bytes, d_csizes, d_offsets, s,
+        [&] {
+            return lzh_launch_zstd_dfast_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs,
+                                              d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k,
+                                              base + t.recs, t.rec_stride, s);
+        },
+        [&] {
+            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
+                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
+        });
+}
+
+int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out) {
+    if (!out || !zstd_dfast_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    return lzh_zstd_dfast_dict_params(level, n, dict_bytes, out) ? LZH_OK : LZH_EARG;
+}
+
+long lzh_debug_zstd_dfast_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
+                                     uint32_t* seqs, size_t cap, uint64_t* events) {
+    if (!dict || (!src && n) || (!seqs && cap) || !zstd_dfast_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    return lzh_zstd_dfast_dict_host_parse(level, (const uint8_t*)dict, dict_bytes, (const uint8_t*)src, n, seqs, cap,
+                                          events);
+}
+
 // ---- 3c. ragged zstd batches: entry points of their own (the calls of 3b keep refusing zstd) ----
 // compress temp: chunk_temp(zstd) of nchunks staging slots and scratch areas sized for max_chunk_bytes;
 // decompress temp: ragged_decode_temp (its scanned offsets; the one-wave decoder needs no descriptors), or

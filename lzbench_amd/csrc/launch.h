@@ -266,6 +266,30 @@ int lzh_zstd_dict_params(int level, uint64_t n, uint64_t dict_bytes, uint32_t* o
 long lzh_zstd_dict_host_parse(int level, const uint8_t* dict, uint64_t dict_bytes, const uint8_t* src, uint64_t n,
                               uint32_t* seqs, uint64_t cap);
 
+// ragged zstd level-3 batches with a shared dictionary (zstd_dfast_dict_hip.hip, zstd_dfast_dict_parse.h;
+// include/lzbench_hip.h 3h): 3f's limits, level 3 alone.  lzh_zstd_dfast_dict_scratch_stride: a chunk's scratch area
+// (the areas of the zstd kernels' Layout for a block of max_bytes, then the frame's private pair of tables, the largest
+// any frame of the batch can take); lzh_zstd_dfast_dict_tables_bytes: the table region (one filled pair per (hashLog,
+// chainLog, minMatch) class, a constant bound).  The launcher fills the class tables once, then runs the match kernel
+// and the level-3 entropy stage of lzh_launch_zstd_dfast_entropy_ragged (zstd_dfast_ragged_hip.hip: block 0 of
+// lzh_zstd_dfast_entropy_ragged_kernel alone), every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0.
+size_t lzh_zstd_dfast_dict_scratch_stride(size_t dict_bytes, size_t max_bytes);
+size_t lzh_zstd_dfast_dict_tables_bytes(void);
+hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables,
+                                      const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
+                                      uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
+                                      uint8_t* scratch, uint64_t fstride, hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                                int level, uint8_t* stage, uint64_t stride, uint32_t* csizes,
+                                                uint32_t nchunks, uint8_t* scratch, uint64_t fstride, uint64_t seq_off,
+                                                uint64_t lit_off, uint64_t att_off, uint64_t tmp_off, hipStream_t s);
+// host arithmetic for the debug calls: {windowLog, hashLog, chainLog, minMatch, block size} of ZSTD_getParams(3, n,
+// dict_bytes), and the host walk of one chunk ((ll, ml, offBase) triples and, where events is not null, the counters
+// of zfd::Event added to it; the count, -1: arguments)
+int lzh_zstd_dfast_dict_params(int level, uint64_t n, uint64_t dict_bytes, uint32_t* out);
+long lzh_zstd_dfast_dict_host_parse(int level, const uint8_t* dict, uint64_t dict_bytes, const uint8_t* src, uint64_t n,
+                                    uint32_t* seqs, uint64_t cap, uint64_t* events);
+
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
 hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
                                   const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);

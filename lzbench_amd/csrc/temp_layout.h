@@ -100,6 +100,23 @@ static inline ZstdDictTemp zstd_dict_temp(size_t dict_bytes, size_t k, size_t ch
     return t;
 }
 
+// ---- zstd level-3 compression of k chunks with a shared dictionary (3h): 3f's three regions with the level-3 calls'
+// own strides -- the staging slots, k scratch areas (the zstd kernels' areas for a block of `chunk` bytes and the frame's
+// private pair of tables, the largest any frame of the batch can take), the table region (one filled pair per class, a
+// constant bound: lzh_zstd_dfast_dict_tables_bytes).
+static inline ZstdDictTemp zstd_dfast_dict_temp(size_t dict_bytes, size_t k, size_t chunk) {
+    ZstdDictTemp t;
+    TempCursor c;
+    chunk = std::max<size_t>(chunk, 1);                 // (a batch of empty chunks is laid out as one of 1-byte chunks)
+    t.stride = lzh_stage_stride(LZH_CODEC_ZSTD, chunk);
+    t.rec_stride = lzh_zstd_dfast_dict_scratch_stride(dict_bytes, chunk);
+    t.stage = c.take(k * t.stride, kGap);
+    t.recs = c.take(k * t.rec_stride, kGap);
+    t.tabs = c.take(lzh_zstd_dfast_dict_tables_bytes(), kGap);
+    t.total = c.at;
+    return t;
+}
+
 // ---- framed compression: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes:
 //   staging slots | LZ4 sequence records of the blocks, then 8 bytes per block (linked frames: the per-frame
 //   table snapshots instead) | block sizes | block offsets inside their frame

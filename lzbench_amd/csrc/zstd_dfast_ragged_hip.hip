@@ -167,6 +167,19 @@ hipError_t lzh_launch_zstd_dfast_ragged(const void* const* in_ptrs, const uint64
     return hipGetLastError();
 }
 
+// The entropy stage of block 0 alone, for a caller with a match kernel of its own that writes this kernel's scratch
+// layout (zstd_dfast_dict_hip.hip): frames of one block, the parameters the body reads (block size, literal
+// compression) being those of the plain call.
+hipError_t lzh_launch_zstd_dfast_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
+                                                int level, uint8_t* stage, uint64_t stride, uint32_t* csizes,
+                                                uint32_t nchunks, uint8_t* scratch, uint64_t fstride, uint64_t seq_off,
+                                                uint64_t lit_off, uint64_t att_off, uint64_t tmp_off, hipStream_t s) {
+    if (nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_zstd_dfast_entropy_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
+                       level, 0, scratch, fstride, seq_off, lit_off, att_off, tmp_off, stage, stride, csizes);
+    return hipGetLastError();
+}
+
 hipError_t lzh_launch_zstd_dfast_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
                                          int level, uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
                                          const LzhCompactLayout& L, hipStream_t s) {

@@ -1,9 +1,11 @@
-"""The ragged device calls of include/lzbench_hip.h 3b .. 3g as a table: one RaggedCall per async entry point.
+"""The ragged device calls of include/lzbench_hip.h 3b .. 3h as a table: one RaggedCall per async entry point.
 
 The calls share one argument list per direction and differ in a head (the arguments before the chunk arrays), in
 whether the batch's promised total follows max_chunk_bytes, and in their sizing calls.  The ctypes signatures of
 lzbench_amd.SIGNATURES, RaggedCodec's dispatch and the check-order test (tests/test_ragged_calls_abi.py) are all read
-from RAGGED_CALLS: a new call is one more row here.
+from RAGGED_CALLS, the calls of 3b .. 3g.  A later call is one more row in MORE_CALLS: signatures(), COMPRESS and
+DECOMPRESS cover both tuples, while the check-order test and tests/ragged_fake.py stay with the rows they were written
+for (a later call brings its own check-order test).
 """
 from __future__ import annotations
 
@@ -50,7 +52,7 @@ class Sizing(_Call):
 class RaggedCall(_Call):
     symbol: str
     compress: bool                   # (else decompress)
-    family: str                      # RaggedCodec's variant: lz, lz4_dict, zstd, zstd_dfast, zstd_dict
+    family: str                      # RaggedCodec's variant: lz, lz4_dict, zstd, zstd_dfast, zstd_dict, zstd_dfast_dict
     head: Tuple[str, ...]            # of codec, level, dict, dict_bytes
     sizing: Sizing                   # the temp below which the call answers LZH_ESPACE
     promise: bool = False            # the compact layouts: the batch's promised total follows max_chunk_bytes
@@ -122,12 +124,18 @@ RAGGED_CALLS = (
     _d("lzh_zstd_decompress_ragged_split_compact_async", "zstd", (), _ZSTD_SMALL, promise=True,
        roomy=Sizing("lzh_zstd_ragged_decompress_split_compact_temp_bytes", ("total",))),
 )
+MORE_CALLS = (
+    # 3h: zstd level 3 with a shared dictionary (the frames decode with 3f's call)
+    _c("lzh_zstd_dfast_compress_ragged_dict_async", "zstd_dfast_dict", ("level",) + _DICT,
+       Sizing("lzh_zstd_dfast_dict_compress_temp_bytes", ("level", "dict_bytes"))),
+)
+ALL_CALLS = RAGGED_CALLS + MORE_CALLS
 # RaggedCodec's lookup: (family, compact layout) -> the call
-COMPRESS = {(r.family, r.promise): r for r in RAGGED_CALLS if r.compress}
-DECOMPRESS = {(r.family, r.promise): r for r in RAGGED_CALLS if not r.compress}
+COMPRESS = {(r.family, r.promise): r for r in ALL_CALLS if r.compress}
+DECOMPRESS = {(r.family, r.promise): r for r in ALL_CALLS if not r.compress}
 
 
 def signatures() -> dict:
     """The SIGNATURES entries of the calls and of their sizing functions."""
-    every = [f for r in RAGGED_CALLS for f in (r, r.sizing, r.roomy) if f is not None]
+    every = [f for r in ALL_CALLS for f in (r, r.sizing, r.roomy) if f is not None]
     return {f.symbol: f.signature() for f in every}
