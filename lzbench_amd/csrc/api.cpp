@@ -537,27 +537,41 @@ size_t lzh_zstd_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_b
     return zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes) ? ragged_decode_temp(nchunks).total : 0;
 }
 
-int lzh_zstd_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes, const void* const* d_in_ptrs,
-                                        const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes,
-                                        void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
-                                        void* d_temp, size_t temp_bytes, void* hip_stream) {
+// the compress call of 3f and of 3h: the level's own ok, layout and launcher; the scan -> pack of 3c
+static int zstd_dict_compress(bool ok, ZstdDictTemp (*layout)(size_t, size_t, size_t), decltype(&lzh_launch_zstd_dict) launch,
+                              int level, const void* d_dict, size_t dict_bytes, const void* const* d_in_ptrs,
+                              const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes, void* d_packed,
+                              size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                              void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool ok = zstd_dict_ok(level, dict_bytes, max_chunk_bytes);
-    const ZstdDictTemp t = ok ? zstd_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
+    const ZstdDictTemp t = ok ? layout(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
     const uint32_t k = (uint32_t)nchunks;
     uint8_t* base = (uint8_t*)d_temp;
     return ragged_compress(
         ok, nchunks, d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total,
         temp_bytes, d_csizes, d_offsets, s,
         [&] {
-            return lzh_launch_zstd_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs, d_in_bytes,
-                                        max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k, base + t.recs,
-                                        t.rec_stride, s);
+            return launch((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs, d_in_bytes,
+                          max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k, base + t.recs, t.rec_stride, s);
         },
         [&] {
             return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
                                           d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
         });
+}
+
+// the pointer checks of the two host-walk debug calls
+static bool dict_parse_pointers(const void* dict, const void* src, size_t n, const uint32_t* seqs, size_t cap) {
+    return dict && (src || !n) && (seqs || !cap);
+}
+
+int lzh_zstd_compress_ragged_dict_async(int level, const void* d_dict, size_t dict_bytes, const void* const* d_in_ptrs,
+                                        const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes,
+                                        void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
+                                        void* d_temp, size_t temp_bytes, void* hip_stream) {
+    return zstd_dict_compress(zstd_dict_ok(level, dict_bytes, max_chunk_bytes), zstd_dict_temp, lzh_launch_zstd_dict, level,
+                              d_dict, dict_bytes, d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed, packed_cap,
+                              d_csizes, d_offsets, d_temp, temp_bytes, hip_stream);
 }
 
 int lzh_zstd_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
@@ -583,7 +597,7 @@ int lzh_debug_zstd_dict_params(int level, size_t n, size_t dict_bytes, uint32_t*
 
 long lzh_debug_zstd_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n, uint32_t* seqs,
                                size_t cap) {
-    if (!dict || (!src && n) || (!seqs && cap) || !zstd_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    if (!dict_parse_pointers(dict, src, n, seqs, cap) || !zstd_dict_ok(level, dict_bytes, n)) return LZH_EARG;
     return lzh_zstd_dict_host_parse(level, (const uint8_t*)dict, dict_bytes, (const uint8_t*)src, n, seqs, cap);
 }
 
@@ -603,23 +617,9 @@ int lzh_zstd_dfast_compress_ragged_dict_async(int level, const void* d_dict, siz
                                               size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
                                               uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
                                               void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const bool ok = zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes);
-    const ZstdDictTemp t = ok ? zstd_dfast_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        ok, nchunks, d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total,
-        temp_bytes, d_csizes, d_offsets, s,
-        [&] {
-            return lzh_launch_zstd_dfast_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs,
-                                              d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k,
-                                              base + t.recs, t.rec_stride, s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
+    return zstd_dict_compress(zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes), zstd_dfast_dict_temp,
+                              lzh_launch_zstd_dfast_dict, level, d_dict, dict_bytes, d_in_ptrs, d_in_bytes, nchunks,
+                              max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream);
 }
 
 int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out) {
@@ -629,7 +629,7 @@ int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uin
 
 long lzh_debug_zstd_dfast_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
                                      uint32_t* seqs, size_t cap, uint64_t* events) {
-    if (!dict || (!src && n) || (!seqs && cap) || !zstd_dfast_dict_ok(level, dict_bytes, n)) return LZH_EARG;
+    if (!dict_parse_pointers(dict, src, n, seqs, cap) || !zstd_dfast_dict_ok(level, dict_bytes, n)) return LZH_EARG;
     return lzh_zstd_dfast_dict_host_parse(level, (const uint8_t*)dict, dict_bytes, (const uint8_t*)src, n, seqs, cap,
                                           events);
 }

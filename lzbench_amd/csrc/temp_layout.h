@@ -87,17 +87,21 @@ static inline DictTemp lz4_dict_temp(size_t k, size_t chunk) {
 // table region: one filled table per (hashLog, minMatch) class, a constant bound (lzh_zstd_dict_tables_bytes).
 static const size_t kZstdDictMax = (size_t)131072;      // largest dictionary and largest chunk of the dictionary calls
 struct ZstdDictTemp { size_t stride, rec_stride, stage, recs, tabs, total; };
-static inline ZstdDictTemp zstd_dict_temp(size_t dict_bytes, size_t k, size_t chunk) {
+static inline ZstdDictTemp zstd_dict_temp_with(size_t (*scratch_stride)(size_t, size_t), size_t (*tables_bytes)(void),
+                                               size_t dict_bytes, size_t k, size_t chunk) {
     ZstdDictTemp t;
     TempCursor c;
     chunk = std::max<size_t>(chunk, 1);                 // (a batch of empty chunks is laid out as one of 1-byte chunks)
     t.stride = lzh_stage_stride(LZH_CODEC_ZSTD, chunk);
-    t.rec_stride = lzh_zstd_dict_scratch_stride(dict_bytes, chunk);
+    t.rec_stride = scratch_stride(dict_bytes, chunk);
     t.stage = c.take(k * t.stride, kGap);
     t.recs = c.take(k * t.rec_stride, kGap);
-    t.tabs = c.take(lzh_zstd_dict_tables_bytes(), kGap);
+    t.tabs = c.take(tables_bytes(), kGap);
     t.total = c.at;
     return t;
+}
+static inline ZstdDictTemp zstd_dict_temp(size_t dict_bytes, size_t k, size_t chunk) {
+    return zstd_dict_temp_with(lzh_zstd_dict_scratch_stride, lzh_zstd_dict_tables_bytes, dict_bytes, k, chunk);
 }
 
 // ---- zstd level-3 compression of k chunks with a shared dictionary (3h): 3f's three regions with the level-3 calls'
@@ -105,16 +109,7 @@ static inline ZstdDictTemp zstd_dict_temp(size_t dict_bytes, size_t k, size_t ch
 // private pair of tables, the largest any frame of the batch can take), the table region (one filled pair per class, a
 // constant bound: lzh_zstd_dfast_dict_tables_bytes).
 static inline ZstdDictTemp zstd_dfast_dict_temp(size_t dict_bytes, size_t k, size_t chunk) {
-    ZstdDictTemp t;
-    TempCursor c;
-    chunk = std::max<size_t>(chunk, 1);                 // (a batch of empty chunks is laid out as one of 1-byte chunks)
-    t.stride = lzh_stage_stride(LZH_CODEC_ZSTD, chunk);
-    t.rec_stride = lzh_zstd_dfast_dict_scratch_stride(dict_bytes, chunk);
-    t.stage = c.take(k * t.stride, kGap);
-    t.recs = c.take(k * t.rec_stride, kGap);
-    t.tabs = c.take(lzh_zstd_dfast_dict_tables_bytes(), kGap);
-    t.total = c.at;
-    return t;
+    return zstd_dict_temp_with(lzh_zstd_dfast_dict_scratch_stride, lzh_zstd_dfast_dict_tables_bytes, dict_bytes, k, chunk);
 }
 
 // ---- framed compression: frames of F bytes (the chunks) cut into blocks of bs = min(F, B) bytes:

@@ -20,9 +20,11 @@
 //                                    and a single-segment header nothing after the match finder depends on the
 //                                    dictionary.
 //
-// The device functions are those of zstdc_dfast.h (and through it of zstdc.h); no existing kernel's code changes.
+// The device functions are those of zstdc_dfast.h (and through it of zstdc.h); no existing kernel's code changes.  What
+// the match kernel and its launcher share with level 1's (zstd_dict_hip.hip) is zstd_dict_env.h.
 #include "zstdc_dfast.h"
 #include "zstd_dfast_dict_parse.h"
+#include "zstd_dict_env.h"
 
 namespace zfd {
 
@@ -31,57 +33,13 @@ struct ClassArg {
     uint32_t hlog[kClassCountMax], clog[kClassCountMax], mls[kClassCountMax], off[kClassCountMax];
 };
 
-// equal bytes at x[a..] and y[b..], at most maxn; wave-parallel, 256 bytes a round (zc::count_fwd over two views)
-__device__ int count_fwd2(const Bytes& x, int a, const Bytes& y, int b, int maxn, int lane) {
-    int n = 0;
-    while (n < maxn) {
-        const int off = n + 4 * lane;
-        uint32_t first = 64 * 4;
-        if (off < maxn) {
-            const uint32_t v = ld_u32(x.r, a + off + x.sh) ^ ld_u32(y.r, b + off + y.sh);
-            int eq = v ? (int)(__builtin_ctz(v) >> 3) : 4;
-            if (off + eq > maxn) eq = maxn - off;
-            if (eq < 4) first = (uint32_t)(4 * lane + eq);
-        }
-        const uint64_t m = ballot(first < 256u);
-        if (m) return n + (int)rdlane(first, ffs64(m));
-        n += 256;
-    }
-    return maxn;
-}
-
-// bytes equal going backwards from x[a - 1] / y[b - 1], at most maxn
-__device__ int count_bwd2(const Bytes& x, int a, const Bytes& y, int b, int maxn, int lane) {
-    int n = 0;
-    while (n < maxn) {
-        const int k = n + lane;
-        const bool stop = k >= maxn || x.b(a - 1 - k) != y.b(b - 1 - k);
-        const uint64_t m = ballot(stop);
-        if (m) return n + ffs64(m);
-        n += 64;
-    }
-    return maxn;
-}
-
-// ext_block's environment on one wave: uniform loads of the chunk and of the dictionary; the private pair of tables in
-// the frame's scratch (L, S) over the class's shared filled pair (LD, SD)
-struct WaveEnv {
-    const Bytes& in;
-    const Bytes& dict;
-    int D;
+// ext_block's environment on one wave: zde::WaveBytes, 64-bit reads of the chunk and of the dictionary, and the private
+// pair of tables in the frame's scratch (L, S) over the class's shared filled pair (LD, SD)
+struct WaveEnv : zde::WaveBytes {
     zc::GlbTab L, S;
     rsrc_t LD, SD;
-    zc::SeqOut& O;
-    int lane;
-    __device__ __forceinline__ uint32_t r32(int p) const { return p >= 0 ? uni(in.w32(p)) : uni(dict.w32(max(D + p, 0))); }
     __device__ __forceinline__ uint64_t r64(int p) const {
         return p >= 0 ? uni64(zc::ld64(in, p)) : uni64(zc::ld64(dict, max(D + p, 0)));
-    }
-    __device__ __forceinline__ int count_fwd(int a, int b, int maxn) const {
-        return b >= 0 ? count_fwd2(in, a, in, b, maxn, lane) : count_fwd2(in, a, dict, D + b, maxn, lane);
-    }
-    __device__ __forceinline__ int count_bwd(int a, int b, int maxn) const {
-        return b >= 0 ? count_bwd2(in, a, in, b, maxn, lane) : count_bwd2(in, a, dict, D + b, maxn, lane);
     }
     // (both loads are issued before either is used; h < 1 << log of both tables of the pair: inside their descriptors)
     __device__ __forceinline__ uint32_t long_get(uint32_t h) const {
@@ -96,11 +54,6 @@ struct WaveEnv {
     __device__ __forceinline__ void short_put(uint32_t h, uint32_t v) const { if (lane == 0) S.put(h, v); }
     __device__ __forceinline__ void fence() const { L.fence(); }
     __device__ __forceinline__ void event(int) const {}
-    __device__ __forceinline__ void seq(int from, int ll, uint32_t offBase, uint32_t mlen) const {
-        zc::lit_copy(in, from, O.lits, O.nl, ll, lane);
-        O.nl += ll;
-        O.put(lane, (uint32_t)ll, offBase, mlen);
-    }
 };
 
 }  // namespace zfd
@@ -147,7 +100,7 @@ lzh_zstd_dfast_dict_match_kernel(const uint8_t* dict, uint32_t dict_bytes, const
         if (C.hlog[c] == P.hlog && C.clog[c] == P.clog && C.mls[c] == P.mls) toff = C.off[c];
     const uint32_t lbytes = 4u << P.hlog, sbytes = 4u << P.clog;
     if (sn < 7 || !P.ok || toff == ~0u || lbytes + sbytes > tab_cap) {   // ZSTD_buildSeqStore: too small, stored raw
-        if (lane == 0) { st_b32(hdr, 32, 1u); st_b32(hdr, 0, 0u); st_b32(hdr, 4, 0u); }
+        zde::raw_header(hdr, lane);
         return;
     }
     // the frame's private pair starts empty (16 bytes a lane; tab_off is 256-aligned, both sizes multiples of 256)
@@ -159,25 +112,14 @@ lzh_zstd_dfast_dict_match_kernel(const uint8_t* dict, uint32_t dict_bytes, const
     in_b.init(in, (uint64_t)sn + 16);
     dict_b.init(dict, (uint64_t)dict_bytes + 16);
     SeqOut O;
-    O.seq = make_rsrc(fs + seq_off, (uint32_t)(lit_off - seq_off));
-    O.lits.init(fs + lit_off, P.bsize + 64);
-    O.ns = 0;
-    O.nl = 0;
+    zde::seq_store(O, fs, seq_off, lit_off, P.bsize);
     uint32_t rep[2] = {1u, 4u};                          // repStartValue
-    zfd::WaveEnv E{in_b, dict_b, (int)dict_bytes,
+    zfd::WaveEnv E{{in_b, dict_b, (int)dict_bytes, O, lane},
                    GlbTab{make_rsrc(fs + tab_off, lbytes)}, GlbTab{make_rsrc(fs + tab_off + lbytes, sbytes)},
-                   make_rsrc(tables + toff, lbytes), make_rsrc(tables + toff + lbytes, sbytes), O, lane};
+                   make_rsrc(tables + toff, lbytes), make_rsrc(tables + toff + lbytes, sbytes)};
     E.fence();
     const int anchor = zfd::ext_block(E, P, dict_bytes, sn, rep);
-    copy_span(in_b, anchor, O.lits, O.nl, sn - anchor, lane, LZH_WAVE);   // last literals
-    O.nl += sn - anchor;
-    if (lane == 0) {
-        st_b32(hdr, 0, (uint32_t)O.ns);
-        st_b32(hdr, 4, (uint32_t)O.nl);
-        st_b32(hdr, 8, rep[0]);
-        st_b32(hdr, 12, rep[1]);
-        st_b32(hdr, 32, 0u);
-    }
+    zde::close_frame(hdr, in_b, O, anchor, sn, rep, lane);
 }
 
 // ------------------------------------------------------------------------- host side: arithmetic, launchers
@@ -189,9 +131,7 @@ lzh_zstd_dfast_dict_match_kernel(const uint8_t* dict, uint32_t dict_bytes, const
 // never log2(n + dict_bytes) nor 16; monotone in both sizes (the batch's own classes are not: a larger dictionary can
 // drop the small tables)
 static uint32_t dfast_dict_pair_cap(uint64_t dict_bytes, uint64_t max_bytes) {
-    const uint64_t t = dict_bytes + std::max<uint64_t>(max_bytes, 1);
-    uint32_t lg = 6;
-    while ((1ull << lg) < t) lg++;
+    const uint32_t lg = zde::total_log(dict_bytes, max_bytes);
     return (4u << std::min(16u, lg + 1)) + (4u << std::min(16u, lg));
 }
 
@@ -230,26 +170,13 @@ hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, 
     if (K.count > zfd::kClassCountMax || K.bytes > lzh_zstd_dfast_dict_tables_bytes()) return hipErrorInvalidValue;
     if (fstride < lzh_zstd_dfast_dict_scratch_stride(dict_bytes, max_bytes)) return hipErrorInvalidValue;
     zfd::ClassArg C{};
-    C.count = K.count;
-    for (uint32_t i = 0; i < K.count; i++) {
-        C.hlog[i] = K.hlog[i];
-        C.clog[i] = K.clog[i];
-        C.mls[i] = K.mls[i];
-        C.off[i] = K.off[i];
-    }
-    const uint32_t bsize = (uint32_t)std::max<uint64_t>(max_bytes, 1);
-    const Layout Lo = layout_for(bsize, 6);
-    // (every launch on s: a captured call is a chain)
-    hipLaunchKernelGGL(lzh_zstd_dfast_dict_zero_kernel, dim3((K.bytes / 4 + 255) / 256), dim3(256), 0, s,
-                       (uint32_t*)tables, K.bytes / 4);
-    const uint32_t nfill = zdd::fill_count(dict_bytes);
-    if (nfill)
-        hipLaunchKernelGGL(lzh_zstd_dfast_dict_table_kernel, dim3((nfill + 255) / 256, K.count), dim3(256), 0, s, dict,
-                           dict_bytes, nfill, (uint32_t*)tables, C);
-    hipLaunchKernelGGL(lzh_zstd_dfast_dict_match_kernel, dim3(nchunks), dim3(64), 0, s, dict, dict_bytes,
-                       (const uint8_t*)tables, C, in_ptrs, in_bytes, max_bytes, level, scratch, fstride, Lo.seq_off,
-                       Lo.lit_off, Lo.tab_off, dfast_dict_pair_cap(dict_bytes, max_bytes));
-    const hipError_t e = hipGetLastError();
+    zde::fill_class_arg(C, K);
+    for (uint32_t i = 0; i < K.count; i++) C.clog[i] = K.clog[i];
+    const Layout Lo = layout_for((uint32_t)std::max<uint64_t>(max_bytes, 1), 6);
+    const hipError_t e = zde::launch_chain(lzh_zstd_dfast_dict_zero_kernel, lzh_zstd_dfast_dict_table_kernel,
+                                           lzh_zstd_dfast_dict_match_kernel, C, K.bytes, zdd::fill_count(dict_bytes), dict,
+                                           dict_bytes, tables, in_ptrs, in_bytes, max_bytes, level, nchunks, scratch,
+                                           fstride, Lo, dfast_dict_pair_cap(dict_bytes, max_bytes), s);
     if (e != hipSuccess) return e;
     return lzh_launch_zstd_dfast_entropy_ragged(in_ptrs, in_bytes, max_bytes, level, stage, stride, csizes, nchunks,
                                                 scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, s);

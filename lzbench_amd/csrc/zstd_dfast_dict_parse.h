@@ -18,6 +18,8 @@
 //   E.fence()                          table stores before it are visible to table loads after it
 //   E.seq(lit_from, lit_len, offBase, mlen)        one stored sequence and its literals
 //   E.event(k)                         branch k of the list below was reached (the host walk counts; the device ignores)
+//   E.crossed()                        zde::count2 ran on into the chunk: the host walk's event kCrossed
+// The byte side of E -- r32, r64 on the host, the counts, seq -- is zstd_dict_env.h's, shared with zstd_dict_parse.h.
 // Every value the walk branches on is uniform over the callers of one E (a wave on the device).
 #pragma once
 #include <stdint.h>
@@ -48,14 +50,14 @@ struct XParams {
     uint32_t wlog, hlog, clog, mls, bsize;   // hlog: the long table (8-byte hashes); clog: the short one (mls bytes)
 };
 
-ZDF_HD inline bool level_ok(int level) { return level == 3; }
+ZDE_HD inline bool level_ok(int level) { return level == 3; }
 
 // ZSTD_getParams_internal(3, n, D, ZSTD_cpm_noAttachDict) (zstd_compress.c:6272-6295, :1315-1373): the row is chosen
 // by n + D and ZSTD_adjustCParams_internal runs on n + D -- window cut to srcLog, hashLog <= dictAndWindowLog + 1,
 // chainLog <= dictAndWindowLog (ZSTD_cycleLog of dfast is chainLog), window floor 10 -- which is zdf::params_for of a
 // source of n + D bytes: the window already holds dictionary and source (2^wlog >= n + D in every row n + D <= 256 KiB
 // can choose), so ZSTD_dictAndWindowLog is wlog itself.  The block is the chunk.
-ZDF_HD inline XParams params_for(int level, uint64_t n, uint64_t D) {
+ZDE_HD inline XParams params_for(int level, uint64_t n, uint64_t D) {
     XParams p{};
     if (!level_ok(level)) return p;
     const zdf::DParams R = zdf::params_for(3, n + D);
@@ -85,10 +87,9 @@ struct Classes {
     uint32_t off[16];                      // the class's long table in the table region, in bytes; the short one follows
     uint32_t bytes;                        // of all tables
 };
-ZDF_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
+ZDE_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
     Classes C{};
     if (max_chunk < 1) max_chunk = 1;
-    // the parameters change only where n + D passes a power of two (srcLog; the three table bounds are powers of two)
     uint64_t n = 1;
     while (n <= max_chunk) {
         const XParams P = params_for(level, n, D);
@@ -103,10 +104,7 @@ ZDF_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
             C.count++;
         }
         if (n == max_chunk) break;
-        uint64_t t = 64;                                          // the next n + D that is a power of two plus one
-        while (t < n + D) t <<= 1;
-        const uint64_t next = t + 1 - D;
-        n = next > n && next <= max_chunk ? next : max_chunk;
+        n = zde::next_class_n(n, D, max_chunk);
     }
     return C;
 }
@@ -120,21 +118,12 @@ constexpr uint32_t kClassCountMax = 11;
 // The reference's early return (zstd_double_fast.c:560, prefixStartIndex == dictStartIndex: the dictionary fell out of
 // the window) cannot happen here: n + D never passes 2^windowLog (params_for), so lowLimit stays 2.
 template <class Env>
-ZDF_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2]) {
+ZDE_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2]) {
     const uint32_t psi = 2u + D;                              // prefixStartIndex; dictStartIndex = 2
     const int ilimit = n - 8;
     int ip = 0, anchor = 0;
     uint32_t off1 = rep[0], off2 = rep[1];
-    // ZSTD_count_2segments: the match side may run from the dictionary's end into the chunk's start
-    auto count2 = [&](int a, int m) {
-        if (m >= 0) return E.count_fwd(a, m, n - a);
-        const int room = -m < n - a ? -m : n - a;
-        const int c = E.count_fwd(a, m, room);
-        if (c != -m) return c;
-        const int c2 = E.count_fwd(a + c, 0, n - (a + c));
-        if (c2 > 0) E.event(kCrossed);
-        return c + c2;
-    };
+    auto count2 = [&](int a, int m) { return zde::count2(E, a, m, n); };   // ZSTD_count_2segments (E.crossed: kCrossed)
     // the catch-up loop of the three match kinds: stops at dictStart for a source in the dictionary, else at prefixStart
     auto catch_up = [&](int& ipm, int m, uint32_t& mlen) {
         const int low = m < 0 ? -(int)D : 0;
@@ -230,41 +219,19 @@ ZDF_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2
     return anchor;
 }
 
-// A plain host environment over two byte arrays (16 readable bytes after each), a long table of 1 << hlog and a short
-// table of 1 << clog entries.
-struct HostEnv {
-    const uint8_t* dict;
-    uint32_t D;
-    const uint8_t* src;
+// A plain host environment: zde::HostBytes, a long table of 1 << hlog and a short table of 1 << clog entries, and the
+// event counters.
+struct HostEnv : zde::HostBytes {
     uint32_t* ltab;
     uint32_t* stab;
-    uint32_t* out;      // (ll, ml, offBase) triples, or null
     uint64_t* events;   // kEvents counters, or null
-    uint64_t cap, ns, nl;
-    const uint8_t* at(int p) const { return p >= 0 ? src + p : dict + D + p; }
-    uint32_t r32(int p) const { const uint8_t* q = at(p); return q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24); }
-    uint64_t r64(int p) const { return (uint64_t)r32(p) | ((uint64_t)r32(p + 4) << 32); }
-    int count_fwd(int a, int b, int maxn) const {
-        int c = 0;
-        while (c < maxn && src[a + c] == *at(b + c)) c++;
-        return c;
-    }
-    int count_bwd(int a, int b, int maxn) const {
-        int c = 0;
-        while (c < maxn && src[a - 1 - c] == *at(b - 1 - c)) c++;
-        return c;
-    }
     uint32_t long_get(uint32_t h) const { return ltab[h]; }
     uint32_t short_get(uint32_t h) const { return stab[h]; }
     void long_put(uint32_t h, uint32_t v) const { ltab[h] = v; }
     void short_put(uint32_t h, uint32_t v) const { stab[h] = v; }
     void fence() const {}
     void event(int k) const { if (events) events[k]++; }
-    void seq(int, int ll, uint32_t offBase, uint32_t ml) {
-        if (out && ns < cap) { out[3 * ns] = (uint32_t)ll; out[3 * ns + 1] = ml; out[3 * ns + 2] = offBase; }
-        ns++;
-        nl += (uint64_t)ll;
-    }
+    void crossed() const { event(kCrossed); }
 };
 
 // The host walk of one chunk: fills both tables from the dictionary, parses; returns the number of sequences (the
@@ -278,7 +245,7 @@ inline long host_walk(int level, const uint8_t* dict, uint64_t D, const uint8_t*
     uint32_t* ltab = tab;
     uint32_t* stab = tab + (1u << P.hlog);
     for (uint32_t i = 0; i < (1u << P.hlog) + (1u << P.clog); i++) tab[i] = 0;
-    HostEnv E{dict, (uint32_t)D, src, ltab, stab, seqs, events, cap, 0, 0};
+    HostEnv E{{dict, (uint32_t)D, src, seqs, cap, 0, 0}, ltab, stab, events};
     const uint32_t nfill = zdd::fill_count(D);
     for (uint32_t q = 0; q < nfill; q++) {
         const uint64_t v = E.r64((int)(3 * q) - (int)D);

@@ -19,15 +19,13 @@
 //   E.get(h) / E.put(h, idx)           the frame's table, a copy of the dictionary's filled table
 //   E.fence()                          table stores before it are visible to table loads after it
 //   E.seq(lit_from, lit_len, offBase, mlen)        one stored sequence and its literals
+//   E.crossed()                        a forward count ran from the dictionary's end on into the chunk (zde::count2)
+// The byte side of E -- r32, the counts, seq, crossed -- is zstd_dict_env.h's, for the host and for the device.
 // Every value the walk branches on is uniform over the callers of one E (a wave on the device).
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define ZDD_HD __host__ __device__
-#else
-#define ZDD_HD
-#endif
+#include "zstd_dict_env.h"
 
 namespace zdd {
 
@@ -38,12 +36,12 @@ struct XParams {
     uint32_t wlog, hlog, mls, tlen, bsize;
 };
 
-ZDD_HD inline bool level_ok(int level) { return level == 1 || (level <= -1 && level >= -5); }
+ZDE_HD inline bool level_ok(int level) { return level == 1 || (level <= -1 && level >= -5); }
 
 // ZSTD_getParams_internal(level, n, D, ZSTD_cpm_noAttachDict) (zstd_compress.c:6272-6295, :1315-1373) for the levels
 // whose row is ZSTD_fast in all four tables; clevels.h rows 0 and 1 as {W, H, minMatch, targetLength}.
 // n + D <= 256 KiB here, so table 0 is never chosen.
-ZDD_HD inline XParams params_for(int level, uint64_t n, uint64_t D) {
+ZDE_HD inline XParams params_for(int level, uint64_t n, uint64_t D) {
     const uint8_t rows[4][2][4] = {
         {{19, 13, 6, 1}, {19, 14, 7, 0}},
         {{18, 13, 5, 1}, {18, 14, 6, 0}},
@@ -74,7 +72,7 @@ ZDD_HD inline XParams params_for(int level, uint64_t n, uint64_t D) {
 }
 
 // ZSTD_hashPtr on the 8 bytes at a position
-ZDD_HD inline uint32_t hashp(uint64_t v, uint32_t hlog, uint32_t mls) {
+ZDE_HD inline uint32_t hashp(uint64_t v, uint32_t hlog, uint32_t mls) {
     switch (mls) {
         case 5: return (uint32_t)(((v << 24) * 889523592379ull) >> (64 - hlog));
         case 6: return (uint32_t)(((v << 16) * 227718039650203ull) >> (64 - hlog));
@@ -86,7 +84,7 @@ ZDD_HD inline uint32_t hashp(uint64_t v, uint32_t hlog, uint32_t mls) {
 // ZSTD_loadDictionaryContent + ZSTD_fillHashTable(ZSTD_dtlm_fast) (zstd_compress.c:4233-4253, zstd_fast.c:15-43): a
 // dictionary of at most 8 bytes is referenced but not indexed; otherwise dictionary byte positions 0, 3, 6, .. below
 // D - 9 are inserted, a later one replacing an earlier one: an entry is the largest inserted index of its bucket.
-ZDD_HD inline uint32_t fill_count(uint64_t D) { return D <= 8 || D < 10 ? 0u : (uint32_t)((D - 10) / 3 + 1); }
+ZDE_HD inline uint32_t fill_count(uint64_t D) { return D <= 8 || D < 10 ? 0u : (uint32_t)((D - 10) / 3 + 1); }
 
 // The (hashLog, minMatch) classes a batch can take: every n in 1 .. max_chunk with the dictionary of D bytes.
 struct Classes {
@@ -94,10 +92,9 @@ struct Classes {
     uint32_t hlog[16], mls[16], off[16];   // off: the class's table in the table region, in bytes
     uint32_t bytes;                        // of all tables
 };
-ZDD_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
+ZDE_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
     Classes C{};
     if (max_chunk < 1) max_chunk = 1;
-    // the parameters change only where n + D passes a power of two (srcLog; the three table bounds are powers of two)
     uint64_t n = 1;
     while (n <= max_chunk) {
         const XParams P = params_for(level, n, D);
@@ -111,10 +108,7 @@ ZDD_HD inline Classes classes_for(int level, uint64_t D, uint64_t max_chunk) {
             C.count++;
         }
         if (n == max_chunk) break;
-        uint64_t t = 64;                                          // the next n + D that is a power of two plus one
-        while (t < n + D) t <<= 1;
-        const uint64_t next = t + 1 - D;
-        n = next > n && next <= max_chunk ? next : max_chunk;
+        n = zde::next_class_n(n, D, max_chunk);
     }
     return C;
 }
@@ -124,20 +118,13 @@ constexpr uint32_t kClassBytesMax = 4u * ((1u << 16) - (1u << 7)) + (4u << 13) +
 // The parse of the frame's block [0, n), 7 <= n <= 128 KiB, with a dictionary of D bytes.  The literals after the last
 // sequence ([return value, n)) are the caller's to store.
 template <class Env>
-ZDD_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2]) {
+ZDE_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2]) {
     const uint32_t psi = 2u + D;                              // prefixStartIndex; dictStartIndex = 2
     const int ilimit = n - 8;
     const int step0 = (int)(P.tlen + !P.tlen);
     int ip = 0, anchor = 0;
     uint32_t off1 = rep[0], off2 = rep[1];
-    // ZSTD_count_2segments: the match side may run from the dictionary's end into the chunk's start
-    auto count2 = [&](int a, int m) {
-        if (m >= 0) return E.count_fwd(a, m, n - a);
-        const int room = -m < n - a ? -m : n - a;
-        const int c = E.count_fwd(a, m, room);
-        if (c != -m) return c;
-        return c + E.count_fwd(a + c, 0, n - (a + c));
-    };
+    auto count2 = [&](int a, int m) { return zde::count2(E, a, m, n); };   // ZSTD_count_2segments
     while (ip < ilimit) {
         const uint32_t h = hashp(E.r64(ip), P.hlog, P.mls);
         const uint32_t midx = E.get(h);
@@ -194,35 +181,12 @@ ZDD_HD int ext_block(Env& E, const XParams& P, uint32_t D, int n, uint32_t rep[2
     return anchor;
 }
 
-// A plain host environment over two byte arrays (16 readable bytes after each) and a table of 1 << hlog entries.
-struct HostEnv {
-    const uint8_t* dict;
-    uint32_t D;
-    const uint8_t* src;
+// A plain host environment: zde::HostBytes and a table of 1 << hlog entries.
+struct HostEnv : zde::HostBytes {
     uint32_t* tab;
-    uint32_t* out;      // (ll, ml, offBase) triples, or null
-    uint64_t cap, ns, nl;
-    const uint8_t* at(int p) const { return p >= 0 ? src + p : dict + D + p; }
-    uint32_t r32(int p) const { const uint8_t* q = at(p); return q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24); }
-    uint64_t r64(int p) const { return (uint64_t)r32(p) | ((uint64_t)r32(p + 4) << 32); }
-    int count_fwd(int a, int b, int maxn) const {
-        int c = 0;
-        while (c < maxn && src[a + c] == *at(b + c)) c++;
-        return c;
-    }
-    int count_bwd(int a, int b, int maxn) const {
-        int c = 0;
-        while (c < maxn && src[a - 1 - c] == *at(b - 1 - c)) c++;
-        return c;
-    }
     uint32_t get(uint32_t h) const { return tab[h]; }
     void put(uint32_t h, uint32_t v) const { tab[h] = v; }
     void fence() const {}
-    void seq(int, int ll, uint32_t offBase, uint32_t ml) {
-        if (out && ns < cap) { out[3 * ns] = (uint32_t)ll; out[3 * ns + 1] = ml; out[3 * ns + 2] = offBase; }
-        ns++;
-        nl += (uint64_t)ll;
-    }
 };
 
 // The host walk of one chunk: fills the table from the dictionary, parses; returns the number of sequences (the
@@ -233,12 +197,10 @@ inline long host_walk(int level, const uint8_t* dict, uint64_t D, const uint8_t*
     if (n < 7) return 0;                                      // ZSTD_buildSeqStore: too small, no parse
     const XParams P = params_for(level, n, D);
     for (uint32_t i = 0; i < (1u << P.hlog); i++) tab[i] = 0;
-    HostEnv E{dict, (uint32_t)D, src, tab, seqs, cap, 0, 0};
+    HostEnv E{{dict, (uint32_t)D, src, seqs, cap, 0, 0}, tab};
     const uint32_t nfill = fill_count(D);
     for (uint32_t q = 0; q < nfill; q++) {
-        const int p = (int)(3 * q) - (int)D;
-        const uint64_t v = (uint64_t)E.r32(p) | ((uint64_t)E.r32(p + 4) << 32);
-        tab[hashp(v, P.hlog, P.mls)] = 2u + 3u * q;
+        tab[hashp(E.r64((int)(3 * q) - (int)D), P.hlog, P.mls)] = 2u + 3u * q;
     }
     uint32_t rep[2] = {1u, 4u};
     ext_block(E, P, (uint32_t)D, (int)n, rep);

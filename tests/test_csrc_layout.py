@@ -143,7 +143,23 @@ def test_makefile_names_no_compressor_file_as_a_prerequisite():
             assert unit not in prereq.split(), line
 
 
-@pytest.mark.parametrize("header", COMPRESS_HEADERS)
+# The zstd dictionary compressors (levels 1 and 3): what stands around their two walks is zstd_dict_env.h, once.
+DICT_ENV = "zstd_dict_env.h"
+
+
+def test_both_dictionary_units_include_the_shared_environment():
+    src = _sources()
+    for f in ("zstd_dict_hip.hip", "zstd_dfast_dict_hip.hip"):
+        assert '#include "%s"' % DICT_ENV in src[f], f
+    assert "__global__" not in src[DICT_ENV]
+
+
+def test_two_view_counts_are_defined_once():
+    for name in ("count_fwd2", "count_bwd2"):
+        assert [f for f, s in _sources().items() if re.search(r"^__device__ .*\b%s\(" % name, s, re.M)] == [DICT_ENV]
+
+
+@pytest.mark.parametrize("header", COMPRESS_HEADERS + (DICT_ENV,))
 def test_compress_header_compiles_when_included_first(header, tmp_path):
     r = _syntax_check(tmp_path, '#include "%s"\n' % header)
     assert r.returncode == 0, r.stderr

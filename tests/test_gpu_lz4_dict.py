@@ -4,6 +4,7 @@ the reference build's own LZ4_loadDict + LZ4_compress_fast_continue and LZ4_deco
 import numpy as np
 import pytest
 
+from dict_batches import layout, roundtrip, to_dev
 import lz4_dict_inputs as I
 import lz4_dict_ref as R
 import lzbench_amd as L
@@ -11,7 +12,6 @@ from lz_streams import Lz4Writer
 
 pytestmark = pytest.mark.gpu
 
-SLACK = 64
 MAXB = 200000
 
 
@@ -24,17 +24,6 @@ def torch_cuda():
     return torch
 
 
-def layout(sizes, gap=5):
-    """Offsets for chunks of `sizes` in one flat buffer: gaps between chunks, pointers over all residues mod 4."""
-    offs, pos = [], 0
-    for i, s in enumerate(sizes):
-        pos += gap
-        pos += ((1, 2, 3, 0)[i % 4] - pos) % 4
-        offs.append(pos)
-        pos += s
-    return np.array(offs, np.int64), pos + SLACK
-
-
 def place(parts):
     sizes = [len(p) for p in parts]
     offs, total = layout(sizes)
@@ -42,12 +31,6 @@ def place(parts):
     for o, p in zip(offs, parts):
         host[o: o + len(p)] = p
     return host, offs, sizes
-
-
-def to_dev(torch, a: np.ndarray, pad=0):
-    t = torch.zeros(len(a) + pad, dtype=torch.uint8, device="cuda")
-    t[: len(a)].copy_(torch.from_numpy(np.array(a, np.uint8)))
-    return t
 
 
 def codec(torch, d: np.ndarray, maxb, k, acc=1, residue=0):
@@ -77,23 +60,6 @@ def check_batch(torch, rc, d, parts, acc, skip=()):
         assert int(cs[i]) == len(e), f"chunk {i} ({len(parts[i])} bytes): csize {cs[i]}, reference {len(e)}"
         assert packed[of[i]: of[i + 1]].tobytes() == e, f"chunk {i} ({len(parts[i])} bytes): packed bytes differ"
     return cs, of, packed
-
-
-def roundtrip(torch, rc, host, offs, sizes, skip=(), **kw):
-    out = torch.full((len(host),), 0xEE, dtype=torch.uint8, device="cuda")
-    rc.decompress(out, offs, sizes, **kw)
-    torch.cuda.synchronize()
-    st = rc.status[: len(sizes)].cpu().numpy()
-    got = out.cpu().numpy()
-    mask = np.zeros(len(host), bool)
-    for i in range(len(sizes)):
-        if i in skip:
-            continue
-        assert int(st[i]) == sizes[i], f"chunk {i}: status {st[i]}"
-        assert (got[offs[i]: offs[i] + sizes[i]] == host[offs[i]: offs[i] + sizes[i]]).all(), f"chunk {i}: roundtrip"
-        mask[offs[i]: offs[i] + sizes[i]] = True
-    assert (got[~mask] == 0xEE).all(), "the decoder wrote outside the chunks"
-    return st
 
 
 def ref_packed(d, parts, acc):

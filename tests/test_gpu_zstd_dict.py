@@ -5,14 +5,13 @@ module's pure-Python model (tests/test_zstd_dict_frames.py holds the model to th
 import numpy as np
 import pytest
 
+from dict_batches import layout, roundtrip, to_dev
 import lzbench_amd as L
 import zstd_dict_frames as F
 import zstd_dict_inputs as I
 import zstd_dict_ref as R
 
 pytestmark = pytest.mark.gpu
-
-SLACK = 64
 
 
 @pytest.fixture(scope="module")
@@ -24,17 +23,6 @@ def torch_cuda():
     return torch
 
 
-def layout(sizes, gap=5):
-    """Offsets for chunks of `sizes` in one flat buffer: gaps between chunks, pointers over all residues mod 4."""
-    offs, pos = [], 0
-    for i, s in enumerate(sizes):
-        pos += gap
-        pos += ((1, 2, 3, 0)[i % 4] - pos) % 4
-        offs.append(pos)
-        pos += s
-    return np.array(offs, np.int64), pos + SLACK
-
-
 def place(parts):
     sizes = [len(p) for p in parts]
     offs, total = layout(sizes)
@@ -42,12 +30,6 @@ def place(parts):
     for o, p in zip(offs, parts):
         host[o: o + len(p)] = p
     return host, offs, sizes
-
-
-def to_dev(torch, a: np.ndarray, pad=0):
-    t = torch.zeros(len(a) + pad, dtype=torch.uint8, device="cuda")
-    t[: len(a)].copy_(torch.from_numpy(np.array(a, np.uint8)))
-    return t
 
 
 def codec(torch, d: np.ndarray, maxb, k, level=1, residue=0):
@@ -77,23 +59,6 @@ def check_batch(torch, rc, d, parts, level, skip=()):
         assert int(cs[i]) == len(e), f"chunk {i} ({len(parts[i])} bytes): csize {cs[i]}, reference {len(e)}"
         assert packed[of[i]: of[i + 1]].tobytes() == e, f"chunk {i} ({len(parts[i])} bytes): packed bytes differ"
     return cs, of, packed
-
-
-def roundtrip(torch, rc, host, offs, sizes, skip=(), **kw):
-    out = torch.full((len(host),), 0xEE, dtype=torch.uint8, device="cuda")
-    rc.decompress(out, offs, sizes, **kw)
-    torch.cuda.synchronize()
-    st = rc.status[: len(sizes)].cpu().numpy()
-    got = out.cpu().numpy()
-    mask = np.zeros(len(host), bool)
-    for i in range(len(sizes)):
-        if i in skip:
-            continue
-        assert int(st[i]) == sizes[i], f"chunk {i}: status {st[i]}"
-        assert (got[offs[i]: offs[i] + sizes[i]] == host[offs[i]: offs[i] + sizes[i]]).all(), f"chunk {i}: roundtrip"
-        mask[offs[i]: offs[i] + sizes[i]] = True
-    assert (got[~mask] == 0xEE).all(), "the decoder wrote outside the chunks"
-    return st
 
 
 def ref_packed(d, parts, level, plain=False):
