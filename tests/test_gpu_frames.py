@@ -11,18 +11,10 @@ import pytest
 import frame_cases as F
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
 NAME = {"lz4f": "lz4frame", "nvlz4": "nvcomp_lz4"}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 @pytest.mark.parametrize("case", F.golden(), ids=F.key)

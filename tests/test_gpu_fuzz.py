@@ -8,6 +8,7 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +17,11 @@ N_STREAMS = 1024
 
 
 @pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
+def torch_cuda_ref(torch_cuda):
+    """torch_cuda where the reference decoders are present: they are this file's checker"""
     if not O.have_ref():
         pytest.skip("reference build (oracle/_ref) not present")
-    torch.cuda.set_device(0)
-    return torch
+    return torch_cuda
 
 
 def _corrupt(rng, s: bytes) -> bytes:
@@ -72,8 +70,8 @@ def _ref_verdict(codec, s: bytes):
 
 @pytest.mark.parametrize("codec", ["lz4", "snappy"])
 @pytest.mark.parametrize("corpus", ["text", "json"])
-def test_corrupt_streams_match_reference_verdicts(torch_cuda, codec, corpus):
-    torch = torch_cuda
+def test_corrupt_streams_match_reference_verdicts(torch_cuda_ref, codec, corpus):
+    torch = torch_cuda_ref
     rng = np.random.default_rng(7 + len(codec) + len(corpus))
     data = L.datagen(corpus, 8 * CAP, seed=99)
     packed, cs = O.compress_chunks(data, codec, CAP)

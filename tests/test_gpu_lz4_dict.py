@@ -4,7 +4,7 @@ the reference build's own LZ4_loadDict + LZ4_compress_fast_continue and LZ4_deco
 import numpy as np
 import pytest
 
-from dict_batches import layout, roundtrip, to_dev
+from gpu_batches import check_batch, layout, place, roundtrip, to_dev, torch_cuda
 import lz4_dict_inputs as I
 import lz4_dict_ref as R
 import lzbench_amd as L
@@ -13,24 +13,6 @@ from lz_streams import Lz4Writer
 pytestmark = pytest.mark.gpu
 
 MAXB = 200000
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
-def place(parts):
-    sizes = [len(p) for p in parts]
-    offs, total = layout(sizes)
-    host = np.zeros(total, np.uint8)
-    for o, p in zip(offs, parts):
-        host[o: o + len(p)] = p
-    return host, offs, sizes
 
 
 def codec(torch, d: np.ndarray, maxb, k, acc=1, residue=0):
@@ -43,23 +25,6 @@ def codec(torch, d: np.ndarray, maxb, k, acc=1, residue=0):
         rc.dict_shifted[residue: residue + len(d)].copy_(torch.from_numpy(d))
         rc._head["dict"] = rc.dict_shifted.data_ptr() + residue
     return rc
-
-
-def check_batch(torch, rc, d, parts, acc, skip=()):
-    """csizes, offsets and every packed byte range of rc's last compress call against the reference."""
-    torch.cuda.synchronize()
-    k = len(parts)
-    cs = rc.csizes[:k].cpu().numpy().astype(np.int64)
-    of = rc.offsets[: k + 1].cpu().numpy()
-    assert (of == np.concatenate([[0], np.cumsum(cs)])).all(), "offsets are not the exclusive scan of csizes"
-    packed = rc.packed[: int(of[k])].cpu().numpy()
-    for i in range(k):
-        if i in skip:
-            continue
-        e = R.packed(d, parts[i], acc)
-        assert int(cs[i]) == len(e), f"chunk {i} ({len(parts[i])} bytes): csize {cs[i]}, reference {len(e)}"
-        assert packed[of[i]: of[i + 1]].tobytes() == e, f"chunk {i} ({len(parts[i])} bytes): packed bytes differ"
-    return cs, of, packed
 
 
 def ref_packed(d, parts, acc):
@@ -86,7 +51,7 @@ def test_every_dictionary_with_every_chunk(torch_cuda, matrix, name, d):
         for residue in (0, 1):
             rc = codec(torch, d, MAXB, len(parts), acc, residue)
             rc.compress(d_in, offs, sizes)
-            check_batch(torch, rc, d, parts, acc)
+            check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], acc))
             roundtrip(torch, rc, host, offs, sizes)
         # the reference's own streams, offsets derived on the device
         rp, rcs = ref_packed(d, parts, acc)
@@ -103,7 +68,7 @@ def test_constructed_cases(torch_cuda, name):
     for acc in (1, 7):
         rc = codec(torch, d, max(sizes), 3, acc, residue=acc % 2)
         rc.compress(to_dev(torch, host), offs, sizes)
-        check_batch(torch, rc, d, parts, acc)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], acc))
         roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -116,7 +81,7 @@ def test_small_json_records_compress_better_with_the_dictionary(torch_cuda):
     d_in = to_dev(torch, host)
     rc = codec(torch, d, 4096, 2)
     rc.compress(d_in, offs, sizes)
-    cs, _, _ = check_batch(torch, rc, d, parts, 1)
+    cs, _, _ = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], 1))
     plain = L.RaggedCodec("lz4", 4096, 2)
     plain.compress(d_in, offs, sizes)
     torch.cuda.synchronize()
@@ -139,7 +104,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda):
     temp = torch.full((ct + 2 * G,), 0xA5, dtype=torch.uint8, device="cuda")
     rc.ctemp = temp[G: G + ct]
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, _ = check_batch(torch, rc, d, parts, 1, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], 1), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     assert bool((temp[:G] == 0xA5).all()) and bool((temp[G + ct:] == 0xA5).all()), "write outside the temp buffer"
     stride = L.lib().lzh_stage_stride(L.LZH_CODEC_LZ4, maxb)
@@ -267,7 +232,7 @@ def test_graph_replay(torch_cuda):
 
     def check():
         torch.cuda.synchronize()
-        check_batch(torch, rc, d, parts, 1)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], 1))
         got = out.cpu().numpy()
         assert (rc.status[:k].cpu().numpy() == np.array(sizes)).all()
         for o, s in zip(offs, sizes):

@@ -10,20 +10,12 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
 
 SIZES = ([13, 64, 65, 76, 77] + list(range(83, 97)) + [128 + d for d in (-13, -12, -1, 0, 1, 12, 13)]
          + [4096 - 13, 4096 + 13] + [65536 - d for d in (0, 1, 5, 12, 13, 24, 25, 88, 89)] + [65546, 65547])
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _run_to(n, k):

@@ -23,6 +23,7 @@ import lz_census as Z
 import lz_streams as S
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import to_dev, torch_cuda
 from test_lz_streams import frame_verdict, hc_fixture, reference
 
 pytestmark = pytest.mark.gpu
@@ -30,15 +31,6 @@ WINDOWS = [4096, 8192, 16384]
 NAME = {"lz4f": "lz4frame", "nvlz4": "nvcomp_lz4"}
 
 _ran = Counter()          # the census of every accepted stream a test here decoded
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _hook(name, restype=C.c_int):
@@ -73,18 +65,12 @@ def batches(codec):
     return _batches[codec]
 
 
-def to_dev(torch, blob: bytes):
-    t = torch.zeros(len(blob) + 256, dtype=torch.uint8, device="cuda")
-    t[: len(blob)].copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
-    return t
-
-
 def decode_uniform(torch, codec, cap, streams):
     """the streams as the chunks of one DeviceCodec.decompress call (capacity cap each) -> (statuses, outputs)"""
     k = len(streams)
     dc = L.DeviceCodec(codec, k * cap, cap)
     dc.out.zero_()
-    dc.decompress(packed=to_dev(torch, b"".join(streams)),
+    dc.decompress(packed=to_dev(torch, np.frombuffer(b"".join(streams), np.uint8), 256),
                   csizes=torch.tensor([len(s) for s in streams], dtype=torch.int32, device="cuda"))
     torch.cuda.synchronize()
     return dc.status[:k].cpu().numpy(), dc.out[: k * cap].cpu().numpy().reshape(k, cap)
@@ -135,7 +121,7 @@ def test_ragged_decoder(torch_cuda, codec):
     total = pos + 64
     rc = L.RaggedCodec(codec, max(sizes), len(sizes), max_total_bytes=sum(sizes))
     out = torch.full((total,), 0xEE, dtype=torch.uint8, device="cuda")
-    rc.decompress(out, offs, sizes, packed=to_dev(torch, b"".join(s for _, s, *_ in items)),
+    rc.decompress(out, offs, sizes, packed=to_dev(torch, np.frombuffer(b"".join(s for _, s, *_ in items), np.uint8), 256),
                   csizes=torch.tensor([len(s) for _, s, *_ in items], dtype=torch.int32, device="cuda"))
     torch.cuda.synchronize()
     st = rc.status[: len(sizes)].cpu().numpy()

@@ -30,7 +30,8 @@ import lzbench_amd as L
 import lzc_census as Z
 import lzc_inputs as I
 import oracle_lib as O
-from test_gpu_ragged import check_batch, layout, roundtrip, to_dev, torch_cuda  # noqa: F401  (torch_cuda: the fixture)
+from gpu_batches import check_batch, layout, roundtrip, to_dev, torch_cuda
+from ragged_inputs import expected
 from test_lzc_census import IDS, ROWS, census_of, data_of
 
 pytestmark = pytest.mark.gpu
@@ -104,7 +105,7 @@ def test_ragged_batches(torch_cuda, compact):
             host[o: o + len(p)] = p
         rc = L.RaggedCodec(codec, max(sizes), len(sizes), level, max_total_bytes=sum(sizes), compact=compact)
         rc.compress(to_dev(torch, host), offs, sizes)
-        cs, _, _ = check_batch(torch, rc, host, offs, sizes, codec, level)
+        cs, _, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level))
         roundtrip(torch, rc, host, offs, sizes)
         for j, i in enumerate(inps):
             if i.packed[level] < len(data_of(i)):        # (else stored raw: check_batch held it to the rule)

@@ -8,17 +8,9 @@ import pytest
 import golden_data as G
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def gpu_block(codec, data, acc=1):

@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import lzbench_amd as L
-from test_gpu_ragged import (CASES, CASE_IDS, EDGE_SIZES, check_batch, edge_input, expect, layout, raw_chunk,  # noqa: F401
-                             roundtrip, to_dev, torch_cuda)
+from gpu_batches import check_batch, layout, roundtrip, to_dev, torch_cuda
+from ragged_inputs import CASES, CASE_IDS, EDGE_SIZES, edge_input, expect, expected, raw_chunk
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def test_edge_sizes_in_one_batch(torch_cuda, edge_input, codec, level):
     rc, guard = compact_codec(torch, codec, level, max(EDGE_SIZES), k, sum(EDGE_SIZES))
     d_in = to_dev(torch, host)
     rc.compress(d_in, offs, EDGE_SIZES)
-    check_batch(torch, rc, host, offs, EDGE_SIZES, codec, level)
+    check_batch(torch, rc, len(EDGE_SIZES), expected(host, offs, EDGE_SIZES, codec, level))
     assert guard_intact(torch, guard)
     roundtrip(torch, rc, host, offs, EDGE_SIZES)
     # the uniform-slot call on the same arrays
@@ -64,7 +64,7 @@ def test_equals_the_uniform_slot_call_on_many_small_chunks(torch_cuda, codec, le
     host = L.datagen("mixed", total, seed=37)
     rc, guard = compact_codec(torch, codec, level, 5000, 300, sum(sizes))
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, host, offs, sizes, codec, level)
+    check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level))
     ru = L.RaggedCodec(codec, 5000, 300, level, max_total_bytes=sum(sizes))
     ru.compress_arrays(rc._in, 300)
     same_outputs(torch, rc, ru, 300)
@@ -105,7 +105,7 @@ def test_a_skewed_batch(torch_cuda, skewed_input, codec, level, where):
     # the point of the layout: this batch's temp is a fraction of the uniform slots'
     assert rc.ctemp.numel() * 20 < L.lib().lzh_ragged_compress_temp_bytes(rc.codec, BIG, k)
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, host, offs, sizes, codec, level)
+    check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level))
     assert guard_intact(torch, guard), "write past the sizing answer"
     roundtrip(torch, rc, host, offs, sizes)
 
@@ -134,7 +134,7 @@ def test_incompressible_input_and_the_raw_store_rule(torch_cuda, codec, level):
     assert expect(parts[1], codec, level) == parts[1].tobytes()
     rc, guard = compact_codec(torch, codec, level, 200000, len(sizes), sum(sizes))
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, packed = check_batch(torch, rc, host, offs, sizes, codec, level)
+    cs, of, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level))
     assert int(cs[1]) == 4096 and packed[of[1]: of[2]].tobytes() == parts[1].tobytes()   # stored raw: a copy
     for i in (2, 4, 5):   # random bytes expand: the staging slot is used to the codec's bound
         assert int(cs[i]) > sizes[i]
@@ -166,7 +166,7 @@ def test_a_broken_promise(torch_cuda, edge_input, codec, level):
     d_in = to_dev(torch, host)
     both = np.stack([offs + d_in.data_ptr(), np.array(EDGE_SIZES, np.int64)])
     rc.compress_arrays(torch.from_numpy(both).cuda(), k)      # (compress() refuses the batch on the host)
-    cs, of, _ = check_batch(torch, rc, host, offs, EDGE_SIZES, codec, level, skip=dropped)
+    cs, of, _ = check_batch(torch, rc, len(EDGE_SIZES), expected(host, offs, EDGE_SIZES, codec, level), skip=dropped)
     for i in dropped:
         assert int(cs[i]) == 0 and of[i] == of[i + 1]
     assert guard_intact(torch, guard), "write past the temp buffer"
@@ -188,7 +188,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda, codec, level):
     d_in = to_dev(torch, host)
     both = np.stack([offs + d_in.data_ptr(), np.array(sizes, np.int64)])
     rc.compress_arrays(torch.from_numpy(both).cuda(), len(sizes))
-    cs, of, _ = check_batch(torch, rc, host, offs, sizes, codec, level, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     assert guard_intact(torch, guard), "write past the temp buffer"
     assert bool((pbuf[:GUARD] == 0x5A).all()) and bool((pbuf[GUARD + int(of[4]):] == 0x5A).all()), "write outside packed"
@@ -211,7 +211,7 @@ def test_graph_replay_with_new_data(torch_cuda, codec, level):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         rc.compress_arrays(d_src, k)
-    check_batch(torch, rc, hosts[0], offs, sizes, codec, level)
+    check_batch(torch, rc, len(sizes), expected(hosts[0], offs, sizes, codec, level))
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         rc.compress_arrays(d_src, k)
@@ -220,4 +220,4 @@ def test_graph_replay_with_new_data(torch_cuda, codec, level):
         for t in (rc.packed, rc.csizes, rc.offsets):
             t.zero_()
         g.replay()
-        check_batch(torch, rc, host, offs, sizes, codec, level)
+        check_batch(torch, rc, len(sizes), expected(host, offs, sizes, codec, level))

@@ -11,19 +11,11 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
 
 SIZE = 2 << 20
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _lowent(rng):

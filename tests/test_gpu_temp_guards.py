@@ -6,7 +6,8 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
-from test_gpu_ragged import EDGE_SIZES, check_batch, edge_input, to_dev, torch_cuda  # noqa: F401
+from gpu_batches import check_batch, to_dev, torch_cuda
+from ragged_inputs import EDGE_SIZES, edge_input, expected
 
 pytestmark = pytest.mark.gpu
 
@@ -84,7 +85,7 @@ def test_ragged_decode_temp_at_the_sizing_answer(torch_cuda, edge_input, codec, 
     rc = L.RaggedCodec(codec, maxb, k, level, max_total_bytes=sum(EDGE_SIZES))
     rc.dtemp, guards = guarded(torch, L.lib().lzh_ragged_decompress_temp_bytes(rc.codec, maxb, k))
     rc.compress(to_dev(torch, host), offs, EDGE_SIZES)
-    check_batch(torch, rc, host, offs, EDGE_SIZES, codec, level)
+    check_batch(torch, rc, len(EDGE_SIZES), expected(host, offs, EDGE_SIZES, codec, level))
     for kw in ({}, {"csizes": rc.csizes}):       # the compressor's offsets; offsets=None: scanned into temp
         out = torch.full((len(host),), FILL, dtype=torch.uint8, device="cuda")
         rc.status.fill_(-7)

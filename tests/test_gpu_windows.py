@@ -11,18 +11,10 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 
 pytestmark = pytest.mark.gpu
 WINDOWS = [4096, 8192, 16384]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _force(kw):

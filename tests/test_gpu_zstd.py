@@ -14,18 +14,10 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import torch_cuda
 from test_zstd_golden import arrays, cases, corpus
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 # split: the four kernels (the literal kernel's sections per wave by frame count: 4 for these sizes; streams

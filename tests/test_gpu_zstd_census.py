@@ -20,8 +20,8 @@ import zstd_census as Z
 import zstd_edge_inputs as E
 import zstd_hand_frames as H
 from test_gpu_zstd import PATHS, expected_sizes, gpu_decode
-from test_gpu_zstd_ragged import (check_batch, codec_name, layout, roundtrip, to_dev,
-                                  torch_cuda)  # noqa: F401  (torch_cuda: the fixture)
+from gpu_batches import check_batch, layout, roundtrip, to_dev, torch_cuda
+from zstd_ragged_inputs import codec_name, expected
 from test_gpu_zstd_ragged_split import decode_frames
 from test_zstd_census import (EDGE_ROWS, edge_data, edge_packed, ref_decode, repeat_arrays, repeat_cases,
                               repeat_corpus)
@@ -89,7 +89,7 @@ def test_ragged_batch_of_single_block_inputs(torch_cuda, level):
         rc = L.RaggedCodec(codec_name(level), max(sizes), len(sizes), level, max_total_bytes=sum(sizes),
                            split_decode=split)
         rc.compress(to_dev(torch, host), offs, sizes)
-        cs, of, packed = check_batch(torch, rc, host, offs, sizes, level)
+        cs, of, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
         roundtrip(torch, rc, host, offs, sizes)
     for i, e in enumerate(edges):        # the whole inputs' frames are the uniform call's for a chunk of that size
         assert int(cs[i]) == e.packed[level]

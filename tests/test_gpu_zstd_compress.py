@@ -3,7 +3,6 @@ the reference: every digest of tests/golden/zstd_cgolden.json (the reference zst
 through lzbench's chunk loop) reproduced byte for byte through the batched C-ABI rows, fresh
 inputs equal to the oracle restatement (pinned to the reference by tests/test_zstd_oracle.py),
 the per-chunk lzbench rows, and round trips through the GPU decoder.  Run with -m gpu."""
-import hashlib
 import json
 import os
 
@@ -12,18 +11,10 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import sha, torch_cuda
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def cgolden():
@@ -43,10 +34,6 @@ def corpus(kind, n, seed):
         return np.repeat(rng.integers(0, 4, n // 8 + 16, dtype=np.uint8),
                          rng.integers(1, 300, n // 8 + 16))[:n].copy()
     return L.datagen(kind, n, seed)
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def row_name(level):

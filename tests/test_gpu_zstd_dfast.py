@@ -3,7 +3,6 @@ against the reference: every digest of tests/golden/zstd_dfast_golden.json (the 
 lzbench's chunk loop) reproduced byte for byte through the batched rows and decoded back under both zstd codec names,
 fresh slices and a device-resident batch equal to the reference build byte for byte (those two need oracle/_ref),
 the per-chunk row, and the level check.  Run with -m gpu."""
-import hashlib
 import json
 import os
 
@@ -12,28 +11,16 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import sha, torch_cuda
 import zstd_dfast_cases as Z
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
 def golden():
     with open(os.path.join(GOLD, "zstd_dfast_golden.json")) as f:
         return json.load(f)["cases"]
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def need_ref():

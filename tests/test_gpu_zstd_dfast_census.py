@@ -22,7 +22,7 @@ import oracle_lib as O
 import zstd_dfast_census as D
 import zstd_dfast_inputs as I
 from test_gpu_zstd_dfast_ragged import decode_both, frames, result
-from test_gpu_zstd_ragged import layout, to_dev
+from gpu_batches import layout, sha, to_dev, torch_cuda
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -31,19 +31,6 @@ with open(os.path.join(GOLD, "zstd_dfast_census_golden.json")) as _f:
 SMALL = [i for i in I.INPUTS if i.name != I.FAR]
 _ran = Counter()               # the census of every frame a test here compressed (needs the host walk's library)
 _data = {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def data_of(inp):

@@ -8,19 +8,10 @@ import lzbench_amd as L
 import zstd_dfast_dict_inputs as K
 import zstd_dict_inputs as I
 import zstd_dict_ref as R
-from test_gpu_zstd_dict import check_batch, layout, place, ref_packed, roundtrip, to_dev
+from gpu_batches import check_batch, place, roundtrip, to_dev, torch_cuda
 
 pytestmark = pytest.mark.gpu
 LEVEL = 3
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
 
 
 def codec(torch, d: np.ndarray, maxb, k, residue=0):
@@ -47,7 +38,7 @@ def test_every_dictionary_with_every_chunk(torch_cuda, name, kind, d):
     assert sorted(set(int(o) % 4 for o in offs)) == [0, 1, 2, 3]
     rc = codec(torch, d, 131072, len(parts), residue=len(d) % 4)
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, d, parts, LEVEL)
+    check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], LEVEL))
     roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -60,7 +51,7 @@ def test_constructed_pairs(torch_cuda, name):
     parts = [host[o: o + s] for o, s in zip(offs, sizes)]
     rc = codec(torch, d, max(sizes), 3, residue=len(name) % 4)
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, d, parts, LEVEL)
+    check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], LEVEL))
     roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -79,7 +70,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda):
     temp = torch.full((ct + 2 * G,), 0xA5, dtype=torch.uint8, device="cuda")
     rc.ctemp = temp[G: G + ct]
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, _ = check_batch(torch, rc, d, parts, LEVEL, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], LEVEL), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     assert bool((temp[:G] == 0xA5).all()) and bool((temp[G + ct:] == 0xA5).all()), "write outside the temp buffer"
     stride = lib.lzh_stage_stride(L.LZH_CODEC_ZSTD, maxb)
@@ -100,7 +91,7 @@ def test_packed_cap_one_byte_short(torch_cuda):
     d = I.dictionary("json", 4095)
     parts = [I.chunk("json", 1000), I.chunk("text", 4099), I.chunk("json", 64)]
     host, offs, sizes = place(parts)
-    _, rcs = ref_packed(d, parts, LEVEL)
+    _, rcs = R.packed_batch(d, parts, LEVEL)
     total = int(rcs.sum())
     rc = codec(torch, d, 4099, 3)
     full = torch.full((total + 64,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -125,7 +116,7 @@ def test_small_chunks_and_the_other_decoder(torch_cuda):
     host, offs, sizes = place(parts)
     rc = codec(torch, d, 1000, len(parts), residue=3)
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, packed = check_batch(torch, rc, d, parts, LEVEL)
+    cs, of, packed = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], LEVEL))
     assert int(cs[0]) == 9 and int(cs[5]) == 9, "an empty chunk is the 9-byte frame"
     for i in (1, 2, 6):
         assert packed[of[i]: of[i + 1]].tobytes() == R.packed_plain(parts[i], LEVEL), "under 7 bytes: the plain call's bytes"
@@ -143,7 +134,7 @@ def test_json_records_pack_smaller_than_at_level_1(torch_cuda):
     parts = I.records("json", 256, 1024)
     host, offs, sizes = place(parts)
     d_in = to_dev(torch, host)
-    ref3, ref1 = int(ref_packed(d, parts, 3)[1].sum()), int(ref_packed(d, parts, 1)[1].sum())
+    ref3, ref1 = int(R.packed_batch(d, parts, 3)[1].sum()), int(R.packed_batch(d, parts, 1)[1].sum())
     rc = codec(torch, d, 1100, 256)
     rc.compress(d_in, offs, sizes)
     torch.cuda.synchronize()
@@ -179,7 +170,7 @@ def test_zz_graph_replay(torch_cuda):
 
     def check():
         torch.cuda.synchronize()
-        check_batch(torch, rc, d, parts, LEVEL)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], LEVEL))
         got = out.cpu().numpy()
         assert (rc.status[:k].cpu().numpy() == np.array(sizes)).all()
         for o, s in zip(offs, sizes):

@@ -3,7 +3,6 @@ pointers and sizes through the uniform-slot and the compact layout against the c
 (tests/golden/zstd_dfast_golden.json), the uniform call, the reference build frame by frame, the ragged decoders, and
 the guards of the two calls.  Run with -m gpu."""
 import ctypes as C
-import hashlib
 import json
 import os
 
@@ -13,7 +12,8 @@ import pytest
 import oracle_lib as O
 import lzbench_amd as L
 import zstd_dfast_cases as Z
-from test_gpu_zstd_ragged import SLACK, corpus_mix, layout, roundtrip, to_dev
+from gpu_batches import SLACK, layout, roundtrip, sha, to_dev, torch_cuda
+from zstd_ragged_inputs import corpus_mix
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -21,19 +21,6 @@ MODES = ["uniform", "compact"]
 FAR = "far-copy-then-near-copy-b4096"
 # the ZSTD_getParams size classes and the block boundaries, each with its neighbours
 BOUNDARY = [s + d for s in (64, 16384, 131072, 262144) for d in (-1, 0, 1)]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def codec(mode, maxb, k, total=None, **kw):

@@ -5,31 +5,13 @@ module's pure-Python model (tests/test_zstd_dict_frames.py holds the model to th
 import numpy as np
 import pytest
 
-from dict_batches import layout, roundtrip, to_dev
+from gpu_batches import check_batch, decode_frames, layout, place, roundtrip, to_dev, torch_cuda
 import lzbench_amd as L
 import zstd_dict_frames as F
 import zstd_dict_inputs as I
 import zstd_dict_ref as R
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
-def place(parts):
-    sizes = [len(p) for p in parts]
-    offs, total = layout(sizes)
-    host = np.zeros(total, np.uint8)
-    for o, p in zip(offs, parts):
-        host[o: o + len(p)] = p
-    return host, offs, sizes
 
 
 def codec(torch, d: np.ndarray, maxb, k, level=1, residue=0):
@@ -42,30 +24,6 @@ def codec(torch, d: np.ndarray, maxb, k, level=1, residue=0):
         rc.dict_shifted[residue: residue + len(d)].copy_(torch.from_numpy(d))
         rc._head["dict"] = rc.dict_shifted.data_ptr() + residue
     return rc
-
-
-def check_batch(torch, rc, d, parts, level, skip=()):
-    """csizes, offsets and every packed byte range of rc's last compress call against the reference."""
-    torch.cuda.synchronize()
-    k = len(parts)
-    cs = rc.csizes[:k].cpu().numpy().astype(np.int64)
-    of = rc.offsets[: k + 1].cpu().numpy()
-    assert (of == np.concatenate([[0], np.cumsum(cs)])).all(), "offsets are not the exclusive scan of csizes"
-    packed = rc.packed[: int(of[k])].cpu().numpy()
-    for i in range(k):
-        if i in skip:
-            continue
-        e = R.packed(d, parts[i], level)
-        assert int(cs[i]) == len(e), f"chunk {i} ({len(parts[i])} bytes): csize {cs[i]}, reference {len(e)}"
-        assert packed[of[i]: of[i + 1]].tobytes() == e, f"chunk {i} ({len(parts[i])} bytes): packed bytes differ"
-    return cs, of, packed
-
-
-def ref_packed(d, parts, level, plain=False):
-    """(packed, csizes) as the reference writes the batch, raw-store rule applied"""
-    blocks = [R.packed_plain(p, level) if plain else R.packed(d, p, level) for p in parts]
-    cs = np.array([len(b) for b in blocks], np.int32)
-    return np.frombuffer(b"".join(blocks), np.uint8), cs
 
 
 @pytest.mark.parametrize("name,kind,d", I.dictionaries(), ids=[n for n, _, _ in I.dictionaries()])
@@ -81,7 +39,7 @@ def test_every_dictionary_with_every_chunk(torch_cuda, name, kind, d):
         for residue in (2 * j, 2 * j + 1):
             rc = codec(torch, d, 131072, len(parts), level, residue)
             rc.compress(d_in, offs, sizes)
-            check_batch(torch, rc, d, parts, level)
+            check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], level))
             roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -95,7 +53,7 @@ def test_constructed_cases(torch_cuda, name):
     for level in I.LEVELS:
         rc = codec(torch, d, max(sizes), 3, level, residue=level % 4)
         rc.compress(to_dev(torch, host), offs, sizes)
-        check_batch(torch, rc, d, parts, level)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], level))
         roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -110,9 +68,9 @@ def test_reference_frames_of_other_levels_decode(torch_cuda):
         host, offs, sizes = place(parts)
         rc = codec(torch, d, 131072, len(parts), residue=1)
         for level in (3, 5, 19):
-            rp, rcs = ref_packed(d, parts, level)
+            rp, rcs = R.packed_batch(d, parts, level)
             roundtrip(torch, rc, host, offs, sizes, packed=to_dev(torch, rp, 256), csizes=torch.from_numpy(rcs).cuda())
-        rp, rcs = ref_packed(d, parts, 1, plain=True)
+        rp, rcs = R.packed_batch(d, parts, 1, plain=True)
         roundtrip(torch, rc, host, offs, sizes, packed=to_dev(torch, rp, 256), csizes=torch.from_numpy(rcs).cuda())
 
 
@@ -184,7 +142,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda):
     temp = torch.full((ct + 2 * G,), 0xA5, dtype=torch.uint8, device="cuda")
     rc.ctemp = temp[G: G + ct]
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, _ = check_batch(torch, rc, d, parts, 1, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], 1), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     assert bool((temp[:G] == 0xA5).all()) and bool((temp[G + ct:] == 0xA5).all()), "write outside the temp buffer"
     stride = L.lib().lzh_stage_stride(L.LZH_CODEC_ZSTD, maxb)
@@ -199,7 +157,7 @@ def test_packed_cap_one_byte_short(torch_cuda):
     d = I.dictionary("json", 4095)
     parts = [I.chunk("json", 1000), I.chunk("text", 4099), I.chunk("json", 64)]
     host, offs, sizes = place(parts)
-    _, rcs = ref_packed(d, parts, 1)
+    _, rcs = R.packed_batch(d, parts, 1)
     total = int(rcs.sum())
     rc = codec(torch, d, 4099, 3)
     full = torch.full((total + 64,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -223,7 +181,7 @@ def test_decode_without_offsets_and_equal_bytes_through_the_c_abi(torch_cuda):
     d_in = to_dev(torch, host)
     rc = codec(torch, d, 1000, 4, -3)
     rc.compress(d_in, offs, sizes)
-    cs, of, packed = check_batch(torch, rc, d, parts, -3)
+    cs, of, packed = check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], -3))
     roundtrip(torch, rc, host, offs, sizes, csizes=rc.csizes)          # offsets=None: scanned on the device
     # the same through the C ABI with buffers of this test's own
     lib = L.lib()
@@ -256,8 +214,8 @@ def test_small_json_records_pack_smaller_with_the_dictionary(torch_cuda):
     plain.compress(d_in, offs, sizes)
     torch.cuda.synchronize()
     alone = plain.packed_total()
-    ref_dict = int(ref_packed(d, parts, 1)[1].sum())
-    ref_alone = int(ref_packed(d, parts, 1, plain=True)[1].sum())
+    ref_dict = int(R.packed_batch(d, parts, 1)[1].sum())
+    ref_alone = int(R.packed_batch(d, parts, 1, plain=True)[1].sum())
     print(f"512 JSON records, {sum(sizes)} bytes: {with_dict} with the dictionary, {alone} alone")
     assert with_dict == ref_dict and alone == ref_alone
     assert with_dict < alone
@@ -265,17 +223,6 @@ def test_small_json_records_pack_smaller_with_the_dictionary(torch_cuda):
 
 
 # ---- the hand-built frames (tests/zstd_dict_frames.py): every path of a sequence whose source is the dictionary --
-def decode_frames(torch, rc, frames, caps):
-    """(statuses, the whole output buffer, offsets) of one decode call over hand-made frames, chunk i caps[i] bytes"""
-    offs, total = layout(caps)
-    out = torch.full((total,), 0xEE, dtype=torch.uint8, device="cuda")
-    packed = np.frombuffer(b"".join(frames), np.uint8)
-    rc.decompress(out, offs, caps, packed=to_dev(torch, packed, 256),
-                  csizes=torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda"))
-    torch.cuda.synchronize()
-    return rc.status[: len(frames)].cpu().numpy(), out.cpu().numpy(), offs
-
-
 @pytest.mark.parametrize("residue", [0, 1, 2, 3])
 def test_hand_frames_decode(torch_cuda, residue):
     """one batch of every accepting frame; the expected bytes are the pure-Python model's"""
@@ -353,7 +300,7 @@ def test_the_other_levels(torch_cuda, level):
         host, offs, sizes = place(parts)
         rc = codec(torch, d, max(sizes), len(parts), level, residue=j % 4)
         rc.compress(to_dev(torch, host), offs, sizes)
-        check_batch(torch, rc, d, parts, level)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], level))
         roundtrip(torch, rc, host, offs, sizes)
 
 
@@ -378,7 +325,7 @@ def test_zz_graph_replay(torch_cuda):
 
     def check():
         torch.cuda.synchronize()
-        check_batch(torch, rc, d, parts, 1)
+        check_batch(torch, rc, len(parts), lambda i: R.packed(d, parts[i], 1))
         got = out.cpu().numpy()
         assert (rc.status[:k].cpu().numpy() == np.array(sizes)).all()
         for o, s in zip(offs, sizes):

@@ -2,133 +2,20 @@
 per-chunk pointers and sizes against the CPU restatement and the reference build frame by frame, against the
 uniform call, their guards, and the ragged decoder against reference frames and the uniform verdicts.
 Run with -m gpu."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+import gpu_batches as B
+from gpu_batches import SLACK, check_batch, layout, roundtrip, to_dev, torch_cuda
 from test_zstd_golden import arrays, cases, corpus
+from zstd_ragged_inputs import EDGE_L2, EDGE_SIZES, codec_name, corpus_mix, edge_input, expect, expected
 
 pytestmark = pytest.mark.gpu
 
 ZSTD = L.LZH_CODEC_ZSTD
 LEVELS = [1, -1, -5]
-# 6 | 7: ZSTD_buildSeqStore's raw-block bound; 16384 | 16385, 131072 | 131073, 262144 | 262145: the ZSTD_getParams
-# size classes; 131073 and 262145: the two- and three-block boundaries
-EDGE_SIZES = [0, 1, 6, 7, 8, 255, 4099, 16383, 16384, 16385, 65536, 131071, 131072, 131073, 262144, 262145, 300000]
-EDGE_L2 = [s for s in EDGE_SIZES if s <= 131072]      # level 2 is the fast strategy up to 128 KiB chunks only
-SLACK = 64
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    torch.cuda.set_device(0)
-    return torch
-
-
-def codec_name(level):
-    return "zstd" if level > 0 else "zstd_fast"
-
-
-def corpus_mix(n, seed):
-    """n bytes: datagen("mixed") then datagen("text"), half each"""
-    h = n // 2
-    return np.concatenate([L.datagen("mixed", h, seed=seed), L.datagen("text", n - h, seed=seed + 1)])
-
-
-_empty = None
-_expect_cache = {}
-
-
-def expect(chunk: np.ndarray, level: int) -> bytes:
-    """The packed bytes of one chunk: the frame of the CPU restatement for a chunk of that size alone (raw-store
-    rule applied; cached), checked against the reference build's ZSTD_compress_advanced where that is present.
-    An empty chunk: the reference's frame for 0 bytes (tests/golden/zstd_empty.json)."""
-    global _empty
-    key = (chunk.tobytes(), level)
-    if key not in _expect_cache:
-        if len(chunk) == 0:
-            if _empty is None:
-                with open(os.path.join(GOLD, "zstd_empty.json")) as f:
-                    _empty = json.load(f)["frames"]
-            packed = bytes.fromhex(_empty[str(level)])
-        else:
-            p, cs = O.compress_chunks(np.ascontiguousarray(chunk), "zstd", len(chunk), level, use_ref=False)
-            assert len(cs) == 1 and int(cs[0]) == len(p)
-            packed = p.tobytes()
-        if O.have_ref():
-            src = np.ascontiguousarray(chunk) if len(chunk) else np.zeros(1, np.uint8)
-            dst = np.zeros(len(chunk) + len(chunk) // 128 + 1024, np.uint8)
-            r = O.ref().ref_zstd_compress(src.ctypes.data, len(chunk), dst.ctypes.data, len(dst), level)
-            ref = chunk.tobytes() if r <= 0 or r == len(chunk) else dst[:r].tobytes()
-            assert ref == packed, f"restatement and reference build differ ({len(chunk)} bytes, level {level})"
-        _expect_cache[key] = packed
-    return _expect_cache[key]
-
-
-def layout(sizes, residues=(1, 2, 3, 0), gap=5):
-    """Offsets for chunks of `sizes` in one flat buffer: gaps between chunks, pointers over all residues mod 4."""
-    offs, pos = [], 0
-    for i, s in enumerate(sizes):
-        pos += gap
-        pos += (residues[i % len(residues)] - pos) % 4
-        offs.append(pos)
-        pos += s
-    return np.array(offs, np.int64), pos + SLACK
-
-
-def to_dev(torch, a: np.ndarray, pad=0):
-    t = torch.zeros(len(a) + pad, dtype=torch.uint8, device="cuda")
-    t[: len(a)].copy_(torch.from_numpy(np.array(a, dtype=np.uint8)))   # (a writable copy: frombuffer views are not)
-    return t
-
-
-def check_batch(torch, rc, host, offs, sizes, level, skip=()):
-    """csizes, offsets and every packed byte range of rc's last compress call against expect()."""
-    torch.cuda.synchronize()
-    k = len(sizes)
-    cs = rc.csizes[:k].cpu().numpy().astype(np.int64)
-    of = rc.offsets[: k + 1].cpu().numpy()
-    assert (of == np.concatenate([[0], np.cumsum(cs)])).all(), "offsets are not the exclusive scan of csizes"
-    assert rc.packed_total() == int(cs.sum())
-    packed = rc.packed[: int(of[k])].cpu().numpy()
-    for i in range(k):
-        if i in skip:
-            continue
-        e = expect(host[offs[i]: offs[i] + sizes[i]], level)
-        assert int(cs[i]) == len(e), f"chunk {i} ({sizes[i]} bytes): csize {cs[i]}, expected {len(e)}"
-        assert packed[of[i]: of[i + 1]].tobytes() == e, f"chunk {i} ({sizes[i]} bytes): packed bytes differ"
-    return cs, of, packed
-
-
-def roundtrip(torch, rc, host, offs, sizes, skip=(), **kw):
-    out = torch.full((len(host),), 0xEE, dtype=torch.uint8, device="cuda")
-    rc.decompress(out, offs, sizes, **kw)
-    torch.cuda.synchronize()
-    st = rc.status[: len(sizes)].cpu().numpy()
-    got = out.cpu().numpy()
-    mask = np.zeros(len(host), bool)
-    for i in range(len(sizes)):
-        if i in skip:
-            continue
-        assert int(st[i]) == sizes[i], f"chunk {i}: status {st[i]}"
-        assert (got[offs[i]: offs[i] + sizes[i]] == host[offs[i]: offs[i] + sizes[i]]).all(), f"chunk {i}: roundtrip"
-        mask[offs[i]: offs[i] + sizes[i]] = True
-    assert (got[~mask] == 0xEE).all(), "the decoder wrote outside the chunks"
-    return st
-
-
-@pytest.fixture(scope="module")
-def edge_input():
-    offs, total = layout(EDGE_SIZES)
-    return corpus_mix(total, 21), offs
 
 
 # ---- 1. edge sizes in one batch; 6. the round trip through the ragged decoder --------------------------------
@@ -141,7 +28,7 @@ def test_edge_sizes_in_one_batch(torch_cuda, edge_input, level):
     assert sizes == EDGE_SIZES[: len(sizes)] and sorted(set(int(o) % 4 for o in offs)) == [0, 1, 2, 3]
     rc = L.RaggedCodec(codec_name(level), max(sizes), len(sizes), level, max_total_bytes=sum(sizes))
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, packed = check_batch(torch, rc, host, offs, sizes, level)
+    cs, of, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
     assert int(cs[0]) == 9                          # the empty chunk's frame
     assert [int(c) for c in cs[1:4]] == [1 + 9, 6 + 9, 7 + 9]   # small chunks expand and are not stored raw
     roundtrip(torch, rc, host, offs, sizes)
@@ -181,7 +68,7 @@ def test_order_and_aliasing(torch_cuda, edge_input):
     p_sizes = [EDGE_SIZES[i] for i in perm] + [EDGE_SIZES[16], EDGE_SIZES[16], EDGE_SIZES[9]]
     rc = L.RaggedCodec("zstd", max(EDGE_SIZES), len(p_sizes), level)
     rc.compress(to_dev(torch, host), p_offs, p_sizes)
-    cs, of, packed = check_batch(torch, rc, host, p_offs, p_sizes, level)
+    cs, of, packed = check_batch(torch, rc, len(p_sizes), expected(host, p_offs, p_sizes, level))
     k = len(p_sizes)
     assert packed[of[k - 3]: of[k - 2]].tobytes() == packed[of[k - 2]: of[k - 1]].tobytes()
 
@@ -204,7 +91,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda, level):
     packed = torch.full((rc.max_packed + 2 * G,), 0xEE, dtype=torch.uint8, device="cuda")
     rc.ctemp, rc.packed = temp[G: G + ct], packed[G: G + rc.max_packed]
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, _ = check_batch(torch, rc, host, offs, sizes, level, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     assert bool((temp[:G] == 0xEE).all()) and bool((temp[G + ct:] == 0xEE).all()), "write outside the temp buffer"
     assert bool((packed[:G] == 0xEE).all()) and bool((packed[G + int(of[4]):] == 0xEE).all()), "write outside packed"
@@ -229,7 +116,7 @@ def test_temp_and_packed_cap_guards(torch_cuda):
     rc = L.RaggedCodec("zstd", max(sizes), len(sizes), level, max_total_bytes=sum(sizes))
     d_in = to_dev(torch, host)
     rc.compress(d_in, offs, sizes)
-    cs, of, full = check_batch(torch, rc, host, offs, sizes, level)
+    cs, of, full = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
     k = len(sizes)
     # temp of exactly the sizing answers, followed by guard bytes that stay as they are (compress and decompress)
     G = 4096
@@ -260,15 +147,8 @@ def test_temp_and_packed_cap_guards(torch_cuda):
 # ---- 7. reference frames the encoder never writes ---------------------------------------------------------------
 def decode_frames(torch, frames, out_sizes, maxb):
     """frames (bytes each) as one ragged batch: (status, output canvas, output offsets)"""
-    k = len(frames)
-    rc = L.RaggedCodec("zstd", maxb, k, 1, max_total_bytes=sum(out_sizes))
-    offs, total = layout(out_sizes)
-    out = torch.full((total,), 0xEE, dtype=torch.uint8, device="cuda")
-    packed = to_dev(torch, np.frombuffer(b"".join(frames), np.uint8), 256)
-    csizes = torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda")
-    rc.decompress(out, offs, out_sizes, packed=packed, csizes=csizes, offsets=None)
-    torch.cuda.synchronize()
-    return rc.status[:k].cpu().numpy(), out.cpu().numpy(), offs
+    rc = L.RaggedCodec("zstd", maxb, len(frames), 1, max_total_bytes=sum(out_sizes))
+    return B.decode_frames(torch, rc, frames, out_sizes)
 
 
 def test_reference_frames(torch_cuda):
@@ -379,7 +259,7 @@ def test_graph_replay(torch_cuda):
 
     def check():
         torch.cuda.synchronize()
-        _, _, packed = check_batch(torch, rc, host, offs, sizes, level)
+        _, _, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
         got = out.cpu().numpy()
         assert (rc.status[:k].cpu().numpy() == np.array(sizes)).all()
         for o, s in zip(offs, sizes):

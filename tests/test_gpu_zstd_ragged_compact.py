@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import lzbench_amd as L
-from test_gpu_zstd_ragged import (EDGE_L2, EDGE_SIZES, SLACK, check_batch, codec_name, corpus_mix, edge_input,  # noqa: F401
-                                  layout, roundtrip, to_dev, torch_cuda)
+from gpu_batches import SLACK, check_batch, layout, roundtrip, to_dev, torch_cuda
+from zstd_ragged_inputs import EDGE_L2, EDGE_SIZES, codec_name, corpus_mix, edge_input, expected
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +76,7 @@ def test_edge_sizes_equal_the_uniform_slot_call(torch_cuda, edge_input, level):
     d_in = to_dev(torch, host)
     rc = compact_codec(level, max(sizes), k, sum(sizes))
     rc.compress(d_in, offs, sizes)
-    cs, of, packed = check_batch(torch, rc, host, offs, sizes, level)
+    cs, of, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
     assert int(cs[0]) == 9 and [int(c) for c in cs[1:4]] == [1 + 9, 6 + 9, 7 + 9]
     ru = L.RaggedCodec(codec_name(level), max(sizes), k, level, max_total_bytes=sum(sizes))
     ru.compress(d_in, offs, sizes)
@@ -113,7 +113,7 @@ def test_skewed_batch(torch_cuda, level, k):
     assert rc.ctemp.numel() * 10 < uniform
     temp, packed = with_canary(torch, rc)
     rc.compress(to_dev(torch, host), offs, sizes)
-    cs, of, _ = check_batch(torch, rc, host, offs, sizes, level)
+    cs, of, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
     canary_intact(temp, packed, rc, int(of[k]))
     roundtrip(torch, rc, host, offs, sizes)
 
@@ -136,7 +136,7 @@ def test_oversize_chunk_and_temp_guard(torch_cuda, level):
     d_in = to_dev(torch, host)
     d = torch.from_numpy(np.stack([offs + d_in.data_ptr(), np.array(sizes, np.int64)])).cuda()
     rc.compress_arrays(d, k)
-    cs, of, _ = check_batch(torch, rc, host, offs, sizes, level, skip={1})
+    cs, of, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level), skip={1})
     assert int(cs[1]) == 0 and of[1] == of[2]
     canary_intact(temp, packed, rc, int(of[k]))
     # the oversize chunk took slots of 0 bytes; its neighbours' slots are where the host mirror puts them
@@ -171,7 +171,8 @@ def test_broken_promise_drops_exactly_the_chunks_the_mirror_names(torch_cuda, le
     d = torch.from_numpy(np.stack([offs + d_in.data_ptr(), np.array(sizes, np.int64)])).cuda()
     rc.compress_arrays(d, k)
     dropped = set(range(first, k))
-    cs, of, _ = check_batch(torch, rc, host, offs, sizes, level, skip=dropped)   # (offsets: the scan; [k]: the sum)
+    # (offsets: the scan; [k]: the sum)
+    cs, of, _ = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level), skip=dropped)
     assert all(int(cs[i]) == 0 for i in dropped) and all(int(cs[i]) > 0 for i in range(first))
     assert int(of[k]) == int(cs.sum())
     canary_intact(temp, packed, rc, int(of[k]))
@@ -212,5 +213,5 @@ def test_reuse_of_one_codec(torch_cuda):
         offs, total = layout(sizes)
         host = corpus_mix(total, seed)
         rc.compress(to_dev(torch, host), offs, sizes)
-        check_batch(torch, rc, host, offs, sizes, level)
+        check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
     roundtrip(torch, rc, host, offs, sizes)

@@ -9,8 +9,9 @@ import pytest
 import oracle_lib as O
 import lzbench_amd as L
 from test_zstd_golden import arrays, cases, corpus
-from test_gpu_zstd_ragged import (check_batch, codec_name, corpus_mix, expect, layout, roundtrip, to_dev,
-                                  torch_cuda)  # noqa: F401  (torch_cuda: the fixture)
+import gpu_batches as B
+from gpu_batches import check_batch, layout, roundtrip, to_dev, torch_cuda
+from zstd_ragged_inputs import codec_name, corpus_mix, expect, expected
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,7 @@ def test_edge_sizes_in_one_batch(torch_cuda, edge_input, level):
     zt, dt = split_bytes(maxb, k), small_bytes(maxb, k)
     assert rc.dtemp.numel() == zt > dt > 0
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, host, offs, sizes, level)          # (the frames are the restatement's / the reference's)
+    check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))   # (the restatement's / the reference's frames)
     lib = L.lib()
     big = [i for i, s in enumerate(sizes) if s >= 16384]
     assert len(big) == 6                           # (every frame of 16 KiB and more must end in the split kernels)
@@ -110,7 +111,7 @@ def test_boundary_chunk_sizes(torch_cuda):
         host = corpus_mix(total, 37)
         rc = L.RaggedCodec("zstd", maxb, k, 1, max_total_bytes=sum(sizes), split_decode=True)
         rc.compress(to_dev(torch, host), offs, sizes)
-        check_batch(torch, rc, host, offs, sizes, 1)
+        check_batch(torch, rc, len(sizes), expected(host, offs, sizes, 1))
         if maxb == 16384:
             assert rc.dtemp.numel() == split_bytes(maxb, k) > 0
             guarded_temp(torch, rc, rc.dtemp.numel())
@@ -130,14 +131,9 @@ def decode_frames(torch, frames, out_sizes, maxb, split):
     nbytes = split_bytes(maxb, k) if split else small_bytes(maxb, k)
     assert nbytes > 0 and rc.dtemp.numel() == nbytes
     buf = guarded_temp(torch, rc, nbytes)
-    offs, total = layout(out_sizes)
-    out = torch.full((total,), 0xEE, dtype=torch.uint8, device="cuda")
-    packed = to_dev(torch, np.frombuffer(b"".join(frames), np.uint8), 256)
-    csizes = torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda")
-    rc.decompress(out, offs, out_sizes, packed=packed, csizes=csizes, offsets=None)
-    torch.cuda.synchronize()
+    st, got, offs = B.decode_frames(torch, rc, frames, out_sizes)
     assert bool((buf[nbytes:] == 0xEE).all()), "write past the temp"
-    return rc.status[:k].cpu().numpy(), out.cpu().numpy(), offs, frame_states(rc, maxb, k) if split else None
+    return st, got, offs, frame_states(rc, maxb, k) if split else None
 
 
 def test_reference_frames(torch_cuda):
@@ -235,7 +231,7 @@ def test_oversize_chunk_is_not_processed(torch_cuda):
     host = corpus_mix(total, 17)
     rc = L.RaggedCodec("zstd", maxb, k, 1, max_total_bytes=sum(sizes), split_decode=True)
     rc.compress(to_dev(torch, host), offs, sizes)
-    check_batch(torch, rc, host, offs, sizes, 1, skip={1})
+    check_batch(torch, rc, len(sizes), expected(host, offs, sizes, 1), skip={1})
     zt = split_bytes(maxb, k)
     buf = guarded_temp(torch, rc, zt)
     st = roundtrip(torch, rc, host, offs, sizes, skip={1})    # (chunk 1's bytes count as outside: they keep their fill)
@@ -272,7 +268,7 @@ def test_graph_replay(torch_cuda):
 
     def check():
         torch.cuda.synchronize()
-        _, _, packed = check_batch(torch, rc, host, offs, sizes, level)
+        _, _, packed = check_batch(torch, rc, len(sizes), expected(host, offs, sizes, level))
         got = out.cpu().numpy()
         assert (rc.status[:k].cpu().numpy() == np.array(sizes)).all()
         for o, s in zip(offs, sizes):

@@ -9,8 +9,9 @@ import pytest
 import lzbench_amd as L
 import zstd_hand_frames as H
 from test_zstd_golden import arrays, cases, corpus
-from test_gpu_zstd_ragged import (check_batch, codec_name, corpus_mix, expect, layout, roundtrip, to_dev,
-                                  torch_cuda)  # noqa: F401  (torch_cuda: the fixture)
+import gpu_batches as B
+from gpu_batches import layout, roundtrip, to_dev, torch_cuda
+from zstd_ragged_inputs import codec_name, corpus_mix, expect
 from test_gpu_zstd_ragged_split import EDGE_SIZES, GUARD, LEGACY, SPLIT, guarded_temp, small_bytes, split_bytes
 from test_gpu_zstd_ragged_split import decode_frames as decode_frames_3c
 
@@ -193,14 +194,9 @@ def decode_frames(torch, frames, out_sizes, maxb):
     nbytes = compact_bytes(total, maxb, k)
     assert nbytes > 0 and rc.dtemp.numel() == nbytes
     buf = guarded_temp(torch, rc, nbytes)
-    offs, n = layout(out_sizes)
-    out = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
-    packed = to_dev(torch, np.frombuffer(b"".join(frames), np.uint8), 256)
-    csizes = torch.tensor([len(f) for f in frames], dtype=torch.int32, device="cuda")
-    rc.decompress(out, offs, out_sizes, packed=packed, csizes=csizes, offsets=None)
-    torch.cuda.synchronize()
+    st, got, offs = B.decode_frames(torch, rc, frames, out_sizes)
     assert bool((buf[nbytes:] == 0xEE).all()), "write past the temp"
-    return rc.status[:k].cpu().numpy(), out.cpu().numpy(), offs, states(rc, total, maxb, k)
+    return st, got, offs, states(rc, total, maxb, k)
 
 
 def test_frames_the_encoders_do_not_write(torch_cuda):

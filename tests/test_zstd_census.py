@@ -5,7 +5,6 @@ repeat-mode fixture (tests/golden/make_zstd_repeat.py), the hand-built frames (t
 two REQUIRED sets: from here on they are the statement of what the zstd tests reach.  CPU only; the GPU runs
 the same inputs and frames in tests/test_gpu_zstd_census.py."""
 import functools
-import hashlib
 import json
 import os
 from collections import Counter
@@ -17,6 +16,7 @@ import oracle_lib as O
 import zstd_census as Z
 import zstd_edge_inputs as E
 import zstd_hand_frames as H
+from gpu_batches import sha
 from test_gpu_zstd import _raw_block_frame, _rle_seq_frame
 from test_zstd_golden import arrays, cases
 from test_zstd_oracle import cgolden, corpus as ccorpus
@@ -32,10 +32,6 @@ COMPRESSOR_REQUIRED = set(Z.ALL_CLASSES) - E.COMPRESSOR_NOT_REACHED - E.COMPRESS
 # whose headers are valid and whose second sequence the reference rejects: the 3-byte count is parsed, no valid
 # frame of 128 KiB blocks the decoders are given needs it.)
 DECODER_REQUIRED = set(Z.ALL_CLASSES)
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 # ---- the fixtures and inputs, each compressed once --------------------------------------------------------------

@@ -2,7 +2,6 @@
 tests/golden/zstd_cgolden.json (made by the reference build through lzbench's chunk loop) is
 reproduced by the restatement, and on fresh inputs the restatement equals the reference build
 (oracle/_ref, where present) frame for frame.  CPU only."""
-import hashlib
 import json
 import os
 
@@ -11,6 +10,7 @@ import pytest
 
 import oracle_lib as O
 import lzbench_amd as L
+from gpu_batches import sha
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -32,10 +32,6 @@ def corpus(kind, n, seed):
         return np.repeat(rng.integers(0, 4, n // 8 + 16, dtype=np.uint8),
                          rng.integers(1, 300, n // 8 + 16))[:n].copy()
     return L.datagen(kind, n, seed)
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("case", cgolden(), ids=lambda c: f"{c['corpus']}-{c['n']}-b{c['chunk'] >> 10}-l{c['level']}")

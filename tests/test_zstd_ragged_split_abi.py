@@ -23,7 +23,7 @@ def small_bytes(maxb, k):
     return L.lib().lzh_zstd_ragged_decompress_temp_bytes(maxb, k)
 
 
-def layout(maxb, k):
+def temp_layout(maxb, k):
     out = np.zeros(16, np.uint64)
     rc = L.lib().lzh_debug_zstd_ragged_split_layout(maxb, k, out.ctypes.data)
     return rc, [int(v) for v in out]
@@ -85,7 +85,7 @@ def test_uniform_and_ragged_sizes_differ_by_a_closed_form():
     for maxb in SIZES:
         for k in [c for c in COUNTS if c > 0]:
             jobs = k * ((maxb + 131071) // 131072 + 1) * 64
-            assert layout(maxb, k)[1][13] == jobs, (maxb, k)
+            assert temp_layout(maxb, k)[1][13] == jobs, (maxb, k)
             plan = align(4 * k + 8)             # the uniform call's frame list and two counts
             rounding = align(jobs) - jobs       # the ragged call rounds its jobs region, the uniform one does not
             gaps = 256 - 256                    # the uniform total's trailing gap against the ragged scan region's
@@ -96,7 +96,7 @@ def test_uniform_and_ragged_sizes_differ_by_a_closed_form():
 def test_debug_layout_regions_are_disjoint_and_inside_the_sizing_answer():
     for maxb in (SPLIT_MIN, 70000, 131072, 300000, MAX):
         for k in (0, 1, 9, 1000):
-            rc, v = layout(maxb, k)
+            rc, v = temp_layout(maxb, k)
             assert rc == OK
             total = v[15]
             assert total == split_bytes(maxb, k)
@@ -114,7 +114,7 @@ def test_debug_layout_regions_are_disjoint_and_inside_the_sizing_answer():
             assert by["states"][1] == 4 * k and by["njobs"][1] == 4
             assert by["jobs"][1] >= 64 * k * ((maxb + 131071) // 131072)  # a Huffman job per block
     # a frame's area holds its sequence records, 8 bytes for every 4 bytes of output
-    assert layout(131072, 1)[1][14] >= 2 * 131072
+    assert temp_layout(131072, 1)[1][14] >= 2 * 131072
 
 
 def test_debug_layout_refuses_what_the_sizing_refuses():

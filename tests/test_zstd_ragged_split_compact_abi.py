@@ -22,7 +22,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sizin
 
 def compact_bytes(total, maxb, k):
     """the layout's total (0 where the layout call refuses the size)"""
-    rc, v = layout(total, maxb, k)
+    rc, v = temp_layout(total, maxb, k)
     return v[22] if rc == OK else 0
 
 
@@ -36,7 +36,7 @@ def arrays_bytes(k):
     return 2 * al(4 * k) + 2 * al(8 * (k + 1))
 
 
-def layout(total, maxb, k):
+def temp_layout(total, maxb, k):
     out = np.zeros(23, np.uint64)
     rc = L.lib().lzh_debug_zstd_ragged_split_compact_layout(total, maxb, k, out.ctypes.data)
     return rc, [int(v) for v in out]
@@ -137,7 +137,7 @@ def test_skewed_batch():
 def test_regions_are_disjoint_aligned_and_in_order():
     for total, maxb, k in [(0, SPLIT_MIN, 0), (MAX + 4095 * 4 * KB, MAX, 4096), (9 * 70000, 70000, 9), (MB, BLOCK, 1000),
                            (1 << 36, 300000, 1000), (5, MAX, 1)]:
-        rc, v = layout(total, maxb, k)
+        rc, v = temp_layout(total, maxb, k)
         assert rc == OK
         end = 0
         for i, name in enumerate(REGIONS):
@@ -177,14 +177,14 @@ def test_host_placement_mirror():
         # the promise kept: every chunk in the split kernels; areas and job slots the exclusive scans of the frames'
         # own strides and block slots (so they are disjoint), all inside their regions
         off, job, ins = mirror(sizes, maxb, total)
-        v = layout(total, maxb, k)[1]
+        v = temp_layout(total, maxb, k)[1]
         assert ins == [1] * k, (b, sizes, maxb)
         assert off == want[:-1] and job == wantj[:-1]
         assert want[-1] <= v[3] and wantj[-1] * jb <= v[13]
         # the promise broken: the same scans, and in_split exactly where both ends are inside the smaller regions
         half = total // 2
         off2, job2, ins2 = mirror(sizes, maxb, half)
-        v2 = layout(half, maxb, k)[1]
+        v2 = temp_layout(half, maxb, k)[1]
         assert off2 == off and job2 == job
         for i in range(k):
             area_in = off2[i] + stride(sizes[i]) <= v2[3]

@@ -143,6 +143,13 @@ def packed_plain(chunk: np.ndarray, level: int = 1) -> bytes:
     return _raw_rule(compress_plain(chunk, level), chunk)
 
 
+def packed_batch(dictionary: np.ndarray, parts, level: int = 1, plain=False):
+    """(packed, csizes) as the reference writes the batch, raw-store rule applied"""
+    blocks = [packed_plain(p, level) if plain else packed(dictionary, p, level) for p in parts]
+    cs = np.array([len(b) for b in blocks], np.int32)
+    return np.frombuffer(b"".join(blocks), np.uint8), cs
+
+
 def decompress(dictionary: np.ndarray, frame: bytes, cap: int):
     """(status, bytes) of ZSTD_decompress_usingDict(dst, cap, frame, dictionary): the decoded size, or -1 for an
     error code."""

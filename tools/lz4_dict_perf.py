@@ -10,17 +10,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lzbench_amd as L  # noqa: E402
+from perf_rounds import alternate  # noqa: E402
 
 K, N, WARM, REP = 4096, 4096, 5, 30
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
 
 
 def main():
@@ -33,15 +25,12 @@ def main():
     codecs = (("plain", L.RaggedCodec("lz4", N, K)), ("dict", L.RaggedCodec("lz4", N, K, dictionary=torch.from_numpy(d))))
     arr = {name: (rc._arrays(d_in, offs, sizes, 16), rc._arrays(out, offs, sizes, 0)) for name, rc in codecs}
     torch.cuda.synchronize()
-    t = {(n, w): [] for n, _ in codecs for w in ("compress", "decompress")}
-    for it in range(WARM + REP):
-        for name, rc in codecs:
-            (src, k), (dst, _) = arr[name]
-            c = timed(lambda: rc.compress_arrays(src, k))
-            x = timed(lambda: rc.decompress_arrays(dst, k))
-            if it >= WARM:
-                t[(name, "compress")].append(c)
-                t[(name, "decompress")].append(x)
+    runs = {}
+    for name, rc in codecs:
+        (src, k), (dst, _) = arr[name]
+        runs[(name, "compress")] = lambda rc=rc, src=src, k=k: rc.compress_arrays(src, k)
+        runs[(name, "decompress")] = lambda rc=rc, dst=dst, k=k: rc.decompress_arrays(dst, k)
+    t = alternate(runs, WARM, REP)
     res = {"chunks": K, "chunk_bytes": N, "dict_bytes": len(d), "warmup": WARM, "repeats": REP, "input_bytes": K * N}
     for name, rc in codecs:
         assert (rc.status[:K].cpu().numpy() == N).all()

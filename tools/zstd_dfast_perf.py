@@ -14,18 +14,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import lzbench_amd as L  # noqa: E402
+from perf_rounds import alternate  # noqa: E402
 
 WARM, REP = 3, 30
 WORKLOADS = (("mixed-4096x128KiB", "mixed", 4096 * 131072, 131072), ("text-1GiB-b1024", "text", 1 << 30, 1 << 20))
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
 
 
 def cpu_row(host, chunk):
@@ -44,15 +36,10 @@ def measure(name, kind, n, chunk):
     d_in[:n].copy_(torch.from_numpy(host))
     res = {"corpus": kind, "input_bytes": n, "chunk_bytes": chunk, "warmup": WARM, "repeats": REP}
     codecs = (("zstd_level1", "zstd", 1), ("zstd_dfast_level3", "zstd_dfast", 3))
-    t = {c[0]: [] for c in codecs}
     dcs = {}
     for key, codec, level in codecs:
         dcs[key] = L.DeviceCodec(codec, n, chunk, level=level)
-    for it in range(WARM + REP):
-        for key, _, _ in codecs:
-            ms = timed(lambda: dcs[key].compress(d_in))
-            if it >= WARM:
-                t[key].append(ms)
+    t = alternate({key: lambda key=key: dcs[key].compress(d_in) for key, _, _ in codecs}, WARM, REP)
     for key, _, _ in codecs:
         dc = dcs[key]
         dc.decompress()

@@ -18,24 +18,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import lzbench_amd as L  # noqa: E402
+from perf_rounds import alternate, stats, timed  # noqa: E402
 
 WARM, REP = 3, 20
 LEVELS = (("level3", "zstd_dfast", 3), ("level1", "zstd", 1))
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def stats(v, n):
-    v = np.array(v)
-    return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max()),
-            "GBps": n / float(np.median(v)) / 1e6}
 
 
 def measure(kind, k, chunk, uniform):
@@ -54,12 +40,7 @@ def measure(kind, k, chunk, uniform):
             rc = L.RaggedCodec(codec, chunk, k, level, max_total_bytes=n, compact_scratch=compact)
             d, _ = rc._arrays(d_in, offs, sizes, 16)
             runs[f"{lname}_{vname}"] = (rc, lambda rc=rc, d=d: rc.compress_arrays(d, k), rc.ctemp.numel())
-    t = {key: [] for key in runs}
-    for it in range(WARM + REP):
-        for key, (_, fn, _) in runs.items():
-            ms = timed(fn)
-            if it >= WARM:
-                t[key].append(ms)
+    t = alternate({key: fn for key, (_, fn, _) in runs.items()}, WARM, REP)
     torch.cuda.synchronize()
     first = {}
     for key, (c, _, temp) in runs.items():

@@ -19,24 +19,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import lzbench_amd as L  # noqa: E402
+from perf_rounds import alternate, stats  # noqa: E402
 
 WARM, REP = 3, 20
 DICT = 65536
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def stats(v, n):
-    v = np.array(v)
-    return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max()),
-            "GBps": n / float(np.median(v)) / 1e6}
 
 
 def measure(k, rec, level):
@@ -56,12 +42,7 @@ def measure(k, rec, level):
     for v in rc:
         runs[f"{v}_compress"] = (lambda v=v: rc[v].compress_arrays(src[v], k), n)
         runs[f"{v}_decompress"] = (lambda v=v: rc[v].decompress_arrays(dst[v], k), n)
-    t = {key: [] for key in runs}
-    for it in range(WARM + REP):
-        for key, (fn, _) in runs.items():
-            ms = timed(fn)
-            if it >= WARM:
-                t[key].append(ms)
+    t = alternate({key: fn for key, (fn, _) in runs.items()}, WARM, REP)
     torch.cuda.synchronize()
     res = {"records": k, "record_bytes": rec, "dict_bytes": DICT, "level": level, "input_bytes": n, "warmup": WARM,
            "repeats": REP}
