@@ -971,7 +971,10 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                 // Each lane's candidate: the latest earlier slot member that is inserted when the
                 // lane is probed (ak; -1 = the slot's old value).  Assume prev, resolve the batch,
                 // check the assumption against the resolved inserted set; repeat with corrected
-                // candidates until consistent (each round fixes a prefix of the batch).
+                // candidates until consistent (each round fixes a prefix of the batch: a corrected lane changes A,
+                // le and e of lanes at or above itself only, and links point upward.  Every round still walks from
+                // the batch's first member: keeping the members below the first corrected lane and resuming after
+                // them is correct but measured slower, text +1.5 %, lz4fast,3 +4.9 %, profiles/lz4_walk).
                 const int pv = kC ? prev : -1;
                 int ak = pv;
                 // the lanes whose candidate matches, carried as a uniform mask: a ballot of a merged per-lane bool
@@ -994,6 +997,7 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                     // chain walk (lz4.c:1142-1200: match end -> re-test -> search from ip+1)
                     Mm = 0;
                     endp = false;
+                    LZ_STAT(8, 1);
                     uint64_t E;                                        // probed lanes
                     const uint64_t r0 = A & P0;
                     if (!r0) {
@@ -1004,16 +1008,32 @@ __device__ void compress_chunk(const Bytes& in, int n, const Bytes& out, int acc
                         bool endip = false;                            // a match ended past mflimit
                         // link: next member lane, or 0x80 for the rare cases (long match, parse end)
                         const int link = (lng || (kT && p + kMinMatch + cn >= mfe)) ? 0x80 : f;
+                        // Two members a walk step: each lane's second hop, formed lane-parallel before the walk.  A
+                        // first hop that is no lane (64: the chain leaves the batch, 0x80: a rare case) is the second
+                        // hop too, so the walk stops on the value the member that met it would have given.  The
+                        // gather is a statement of its own, run by every lane: a lane's link is read by the lanes
+                        // before it whatever its own first hop is (inside the select's arm the lanes without a first
+                        // hop are switched off, the gather returns 0 for them and the walk cycles through lane 0).
+                        // Packed for one v_readlane a step: bits 0-5 the first hop's lane, or the lane itself (a bit
+                        // the walk has just set: s_bitset1_b64 takes the low six bits of its index), bits 6-13 the
+                        // second hop.  Text: 7.5 -> 4.1 dependent steps a batch, kernel-only compress -4.0 %, JSON
+                        // -1.9 %, lz4fast,3 -1.6 % (profiles/lz4_walk).
+                        const bool hop = link < LZH_WAVE;
+                        const int hop2 = (int)lane_gather((uint32_t)link, link & (LZH_WAVE - 1));
+                        const int pair = (hop ? link : lane) | ((hop ? hop2 : link) << 6);
                         LZ_CLK(10);                            // (stats: per-lane links)
                         // (links strictly increase, so the walks end)
                         for (;;) {
                             // common case: plain links, one register for the walk (the last member is the
-                            // highest bit of Mm afterwards: members increase) -- 4 instructions a member
+                            // highest bit of Mm afterwards: members increase) -- 7 instructions for two members
                             int fs = unii(sl);
                             Mm = uni64(Mm);   // (uniform already: readfirstlane keeps every instantiation in SGPRs)
                             do {
+                                LZ_STAT(7, 1);
                                 asm("s_bitset1_b64 %0, %1" : "+s"(Mm) : "s"(fs));
-                                fs = rdlanei(link, fs);
+                                const int pk = rdlanei(pair, fs);
+                                asm("s_bitset1_b64 %0, %1" : "+s"(Mm) : "s"(pk));
+                                fs = pk >> 6;
                             } while (fs < LZH_WAVE);
                             sl = 63 - __builtin_clzll(Mm);
                             if (fs != 0x80) break;                     // the chain leaves the batch

@@ -2,7 +2,7 @@
 # tools/exp_build.sh NAME "-DFLAG ..." -- build liblzbench_hip.so with extra defines into build/exp/NAME/
 # (kernel experiments; run with LZH_LIB=build/exp/NAME/liblzbench_hip.so)
 # ONLY="lz4c_hip ..." compiles just those files with the flags and links the in-tree objects (build/obj, from
-# lzbench_amd/csrc/Makefile) for the rest
+# lzbench_amd/csrc/Makefile) for the rest; the units and their per-file flags are the Makefile's
 set -e
 name=$1; flags=$2
 root=$(cd "$(dirname "$0")/.." && pwd)
@@ -10,15 +10,14 @@ out=$root/build/exp/$name
 mkdir -p $out
 cd $root/lzbench_amd/csrc
 objs=""
-for f in lz4c_hip snappyc_hip decode_hip pack_hip zstdc_hip frame_hip; do
-  # per-file flags as in the Makefile; SCHED_<file> (e.g. SCHED_decode_hip) overrides one file's
-  case $f in
-    lz4c_hip) sf="-mllvm -amdgpu-sched-strategy=max-memory-clause" ;;
-    snappyc_hip) sf="-mllvm -amdgpu-sched-strategy=max-memory-clause" ;;
-    zstdc_hip) sf="-mllvm -amdgpu-atomic-optimizer-strategy=None" ;;
-    decode_hip) sf="-mllvm -amdgpu-sched-strategy=max-ilp" ;;
-    *) sf="" ;;
-  esac
+for src in *_hip.hip; do
+  f=${src%.hip}
+  # per-file flags as in the Makefile (SCHED_<unit without _hip>); SCHED_<file> (e.g. SCHED_decode_hip) overrides one
+  sf=$(make -s -f Makefile -f - print_sched U=${f%_hip} <<'EOF'
+print_sched:
+	@echo $(SCHED_$(U))
+EOF
+)
   v=SCHED_$f; [ -n "${!v+x}" ] && sf="${!v}"
   if [ -n "$ONLY" ] && [[ " $ONLY " != *" $f "* ]]; then objs="$objs $root/build/obj/$f.o"; continue; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 $sf $flags -c $f.hip -o $out/$f.o &
