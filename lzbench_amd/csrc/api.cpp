@@ -348,25 +348,41 @@ size_t lzh_ragged_max_packed_bytes(int codec, size_t total_in_bytes, size_t nchu
 
 }  // extern "C"
 
-// The ragged compress calls (3b, 3c, 3d, 3e; uniform slots, compact layout): the argument checks in their order (ok: the
-// codec / level takes max_chunk_bytes; grid_factor: launch blocks per chunk; temp_need: the layout's total), then
-// compress() -> scan -> pack(), the two callables enqueueing on s and returning HIP's verdict.
-template <class Compress, class Pack>
-static int ragged_compress(bool ok, size_t nchunks, bool pointers, size_t grid_factor, size_t temp_need,
-                           size_t temp_bytes, const uint32_t* d_csizes, uint64_t* d_offsets, hipStream_t s,
-                           Compress compress, Pack pack) {
+// the pack launcher of a layout's slots
+static hipError_t launch_pack(const LzhBatch& B, const LzhSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                              uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    return lzh_launch_pack_ragged(B, S, csizes, offsets, packed, packed_cap, s);
+}
+static hipError_t launch_pack(const LzhBatch& B, const LzhCompactSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                              uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    return lzh_launch_pack_compact(B, S, csizes, offsets, packed, packed_cap, s);
+}
+
+// The ragged compress calls (3b .. 3h; uniform slots, compact layout): the argument checks in their order (ok: the
+// codec / level takes max_chunk_bytes; have_dict: the dictionary's pointer, true for a call without one; grid_factor:
+// launch blocks per chunk; t: the call's layout, its total the temp needed), then launch(B, S, s) -> scan -> the pack
+// of the layout's slots, all enqueued on the stream.  B is the batch and S the layout's slots in d_temp, formed only
+// after d_temp has been checked: the launch runs after that too, and adds what offsets of t it needs itself.
+template <class Temp, class Launch>
+static int ragged_compress(bool ok, bool have_dict, size_t grid_factor, const Temp& t, const void* const* d_in_ptrs,
+                           const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes, void* d_packed,
+                           size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                           void* hip_stream, Launch launch) {
     if (!ok) return LZH_EARG;
     if (nchunks == 0) return LZH_OK;
-    if (!pointers) return LZH_EARG;
+    if (!(have_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp)) return LZH_EARG;
     if (nchunks * grid_factor > 0x7fffffffu) return LZH_EARG;   // launch grids
-    if (temp_bytes < temp_need) return LZH_ESPACE;
+    if (temp_bytes < t.total) return LZH_ESPACE;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const LzhBatch B = {d_in_ptrs, d_in_bytes, max_chunk_bytes, (uint32_t)nchunks};
+    const auto S = t.slots((uint8_t*)d_temp);
     {
         Range range("lzh:compress_kernel");
-        LZH_CHECK(compress());
+        LZH_CHECK(launch(B, S, s));
     }
     Range range("lzh:scan_pack");
     LZH_CHECK(lzh_launch_scan(d_csizes, nchunks, d_offsets, nullptr, s));
-    LZH_CHECK(pack());
+    LZH_CHECK(launch_pack(B, S, d_csizes, d_offsets, (uint8_t*)d_packed, packed_cap, s));
     return LZH_OK;
 }
 
@@ -428,25 +444,13 @@ int lzh_compress_ragged_async(int codec, int level, const void* const* d_in_ptrs
                               size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
                               uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
                               void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const ChunkTemp t = chunk_temp(codec, nchunks, max_chunk_bytes);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;   // (null until ragged_compress has checked it: offsets are added after that)
-    return ragged_compress(
-        ragged_ok(codec, max_chunk_bytes), nchunks, d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp,
-        lzh_snappy_ragged_frags(max_chunk_bytes), t.total, temp_bytes, d_csizes, d_offsets, s,
-        [&] {
-            return codec == LZH_CODEC_LZ4
-                       ? lzh_launch_lz4_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level,
-                                               base + t.stage, t.stride, d_csizes, k, base + t.recs, t.rec_stride,
-                                               (uint32_t*)(base + t.hdr), s)
-                       : lzh_launch_snappy_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride,
-                                                  d_csizes, k, base + t.recs, t.rec_stride, (uint32_t*)(base + t.hdr), s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
+    return ragged_compress(ragged_ok(codec, max_chunk_bytes), true, lzh_snappy_ragged_frags(max_chunk_bytes),
+                           chunk_temp(codec, nchunks, max_chunk_bytes), d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes,
+                           d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return codec == LZH_CODEC_LZ4 ? lzh_launch_lz4_ragged(B, level < 1 ? 1 : level, S, d_csizes, s)
+                                                             : lzh_launch_snappy_ragged(B, S, d_csizes, s);
+                           });
 }
 
 int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
@@ -485,23 +489,14 @@ int lzh_lz4_compress_ragged_dict_async(int level, const void* d_dict, size_t dic
                                        const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
                                        size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
                                        uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
     const DictTemp t = lz4_dict_temp(nchunks, max_chunk_bytes);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
     const int acc = level < 1 ? 1 : std::min(level, 65537);   // (LZ4_ACCELERATION_MAX, lz4.c:1578)
-    return ragged_compress(
-        lz4_dict_ok(dict_bytes, max_chunk_bytes), nchunks,
-        d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes,
-        d_csizes, d_offsets, s,
-        [&] {
-            return lzh_launch_lz4_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes, (uint32_t*)(base + t.tab), d_in_ptrs,
-                                       d_in_bytes, max_chunk_bytes, acc, base + t.stage, t.stride, d_csizes, k, s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
+    return ragged_compress(lz4_dict_ok(dict_bytes, max_chunk_bytes), d_dict != nullptr, 1, t, d_in_ptrs, d_in_bytes, nchunks,
+                           max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return lzh_launch_lz4_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes,
+                                                          (uint32_t*)((uint8_t*)d_temp + t.tab), B, acc, S, d_csizes, s);
+                           });
 }
 
 int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
@@ -537,29 +532,6 @@ size_t lzh_zstd_dict_decompress_temp_bytes(size_t dict_bytes, size_t max_chunk_b
     return zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes) ? ragged_decode_temp(nchunks).total : 0;
 }
 
-// the compress call of 3f and of 3h: the level's own ok, layout and launcher; the scan -> pack of 3c
-static int zstd_dict_compress(bool ok, ZstdDictTemp (*layout)(size_t, size_t, size_t), decltype(&lzh_launch_zstd_dict) launch,
-                              int level, const void* d_dict, size_t dict_bytes, const void* const* d_in_ptrs,
-                              const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes, void* d_packed,
-                              size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
-                              void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const ZstdDictTemp t = ok ? layout(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        ok, nchunks, d_dict && d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total,
-        temp_bytes, d_csizes, d_offsets, s,
-        [&] {
-            return launch((const uint8_t*)d_dict, (uint32_t)dict_bytes, base + t.tabs, d_in_ptrs, d_in_bytes,
-                          max_chunk_bytes, level, base + t.stage, t.stride, d_csizes, k, base + t.recs, t.rec_stride, s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
-}
-
 // the pointer checks of the two host-walk debug calls
 static bool dict_parse_pointers(const void* dict, const void* src, size_t n, const uint32_t* seqs, size_t cap) {
     return dict && (src || !n) && (seqs || !cap);
@@ -569,9 +541,14 @@ int lzh_zstd_compress_ragged_dict_async(int level, const void* d_dict, size_t di
                                         const uint64_t* d_in_bytes, size_t nchunks, size_t max_chunk_bytes,
                                         void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
                                         void* d_temp, size_t temp_bytes, void* hip_stream) {
-    return zstd_dict_compress(zstd_dict_ok(level, dict_bytes, max_chunk_bytes), zstd_dict_temp, lzh_launch_zstd_dict, level,
-                              d_dict, dict_bytes, d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed, packed_cap,
-                              d_csizes, d_offsets, d_temp, temp_bytes, hip_stream);
+    const bool ok = zstd_dict_ok(level, dict_bytes, max_chunk_bytes);
+    const ZstdDictTemp t = ok ? zstd_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
+    return ragged_compress(ok, d_dict != nullptr, 1, t, d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed,
+                           packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes,
+                                                           (uint8_t*)d_temp + t.tabs, B, level, S, d_csizes, s);
+                           });
 }
 
 int lzh_zstd_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, const void* d_packed,
@@ -617,9 +594,14 @@ int lzh_zstd_dfast_compress_ragged_dict_async(int level, const void* d_dict, siz
                                               size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
                                               uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
                                               void* hip_stream) {
-    return zstd_dict_compress(zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes), zstd_dfast_dict_temp,
-                              lzh_launch_zstd_dfast_dict, level, d_dict, dict_bytes, d_in_ptrs, d_in_bytes, nchunks,
-                              max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream);
+    const bool ok = zstd_dfast_dict_ok(level, dict_bytes, max_chunk_bytes);
+    const ZstdDictTemp t = ok ? zstd_dfast_dict_temp(dict_bytes, nchunks, max_chunk_bytes) : ZstdDictTemp{};
+    return ragged_compress(ok, d_dict != nullptr, 1, t, d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed,
+                           packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_dfast_dict((const uint8_t*)d_dict, (uint32_t)dict_bytes,
+                                                                 (uint8_t*)d_temp + t.tabs, B, level, S, d_csizes, s);
+                           });
 }
 
 int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uint32_t* out) {
@@ -683,22 +665,11 @@ size_t lzh_zstd_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks) {
 int lzh_zstd_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
                                    size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
                                    uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const ChunkTemp t = zstd_ragged_temp(nchunks, max_chunk_bytes);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        zstd_ragged_ok(level, max_chunk_bytes), nchunks,
-        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
-        d_offsets, s,
-        [&] {
-            return lzh_launch_zstd_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride, d_csizes,
-                                          k, base + t.recs, t.rec_stride, s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
+    return ragged_compress(zstd_ragged_ok(level, max_chunk_bytes), true, 1, zstd_ragged_temp(nchunks, max_chunk_bytes),
+                           d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp,
+                           temp_bytes, hip_stream, [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_ragged(B, level, S, d_csizes, s);
+                           });
 }
 
 int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
@@ -747,20 +718,12 @@ int lzh_debug_zstd_ragged_split_compact_slots(const uint64_t* out_sizes, size_t 
                                               size_t total_out_bytes, uint64_t* area_off, uint64_t* job_off,
                                               uint8_t* in_split) {
     const ZstdRaggedSplitCompactTemp t = zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks);
-    if (!t.ok) return LZH_EARG;
-    if (nchunks == 0) return LZH_OK;
-    if (!out_sizes || !area_off || !job_off || !in_split) return LZH_EARG;
-    uint64_t ao = 0, jo = 0;   // (two exclusive scans, then the check of both ends against their regions)
-    for (size_t i = 0; i < nchunks; i++) {
-        const bool over = out_sizes[i] > max_chunk_bytes;
-        const LzhZsplitRegions sz = over ? LzhZsplitRegions{0, 0} : lzh_zstd_split_compact_slot(out_sizes[i]);
-        area_off[i] = ao;
-        job_off[i] = jo;
-        in_split[i] = !over && ao + sz.areas <= t.reg.areas && jo + sz.jobs <= t.reg.jobs;
-        ao += sz.areas;
-        jo += sz.jobs;
-    }
-    return LZH_OK;
+    // (the areas stand for the staging slots, the job counts for the record slots)
+    return compact_slots_mirror(t.ok, LzhCompactRegions{t.reg.areas, t.reg.jobs}, out_sizes, nchunks, max_chunk_bytes,
+                                area_off, job_off, in_split, [](uint64_t n) {
+                                    const LzhZsplitRegions z = lzh_zstd_split_compact_slot(n);
+                                    return LzhCompactRegions{z.areas, z.jobs};
+                                });
 }
 
 // ---- 3g. the ragged split decoder in that layout: zstd_ragged_split_compact_temp is the sizing answer and what
@@ -824,27 +787,15 @@ int lzh_compress_ragged_compact_async(int codec, int level, const void* const* d
                                       size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes, void* d_packed,
                                       size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp,
                                       size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const CompactTemp t = compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        ragged_ok(codec, max_chunk_bytes), nchunks, d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp,
-        lzh_snappy_ragged_frags(max_chunk_bytes), t.total, temp_bytes, d_csizes, d_offsets, s,
-        [&] {
-            const LzhCompactLayout L = t.layout(base);
-            const hipError_t e = lzh_launch_compact_slots(codec, d_in_bytes, max_chunk_bytes, L, k, s);
-            if (e != hipSuccess) return e;
-            return codec == LZH_CODEC_LZ4
-                       ? lzh_launch_lz4_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level < 1 ? 1 : level,
-                                                base + t.stage, d_csizes, k, base + t.recs, (uint32_t*)(base + t.hdr), L, s)
-                       : lzh_launch_snappy_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, k,
-                                                   base + t.recs, (uint32_t*)(base + t.hdr), L, s);
-        },
-        [&] {
-            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
-                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
-        });
+    return ragged_compress(ragged_ok(codec, max_chunk_bytes), true, lzh_snappy_ragged_frags(max_chunk_bytes),
+                           compact_temp(codec, total_in_bytes, max_chunk_bytes, nchunks), d_in_ptrs, d_in_bytes, nchunks,
+                           max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhCompactSlots& S, hipStream_t s) {
+                               const hipError_t e = lzh_launch_compact_slots(codec, B, S.L, s);
+                               if (e != hipSuccess) return e;
+                               return codec == LZH_CODEC_LZ4 ? lzh_launch_lz4_compact(B, level < 1 ? 1 : level, S, d_csizes, s)
+                                                             : lzh_launch_snappy_compact(B, S, d_csizes, s);
+                           });
 }
 
 // ---- 3c, compact compress layout: every chunk's staging slot and scratch slot sized from its own size and the
@@ -875,23 +826,13 @@ int lzh_zstd_compress_ragged_compact_async(int level, const void* const* d_in_pt
                                            size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
                                            void* d_packed, size_t packed_cap, uint32_t* d_csizes, uint64_t* d_offsets,
                                            void* d_temp, size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const CompactTemp t = zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
     // (the layout's record fields carry the scratch slots: the pack kernel's lookup is the LZ4 / snappy one)
-    return ragged_compress(
-        zstd_ragged_ok(level, max_chunk_bytes), nchunks,
-        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
-        d_offsets, s,
-        [&] {
-            return lzh_launch_zstd_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes, k,
-                                           base + t.recs, t.layout(base), s);
-        },
-        [&] {
-            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
-                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
-        });
+    return ragged_compress(zstd_ragged_ok(level, max_chunk_bytes), true, 1,
+                           zstd_compact_temp(level, total_in_bytes, max_chunk_bytes, nchunks), d_in_ptrs, d_in_bytes, nchunks,
+                           max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhCompactSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_compact(B, level, S, d_csizes, s);
+                           });
 }
 
 // ---- 3e. ragged zstd level-3 batches (the double-fast strategy): entry points of their own -- the calls of 3b keep
@@ -910,22 +851,12 @@ int lzh_zstd_dfast_compress_ragged_async(int level, const void* const* d_in_ptrs
                                          size_t nchunks, size_t max_chunk_bytes, void* d_packed, size_t packed_cap,
                                          uint32_t* d_csizes, uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
                                          void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const ChunkTemp t = zstd_dfast_ragged_temp(nchunks, max_chunk_bytes);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        zstd_dfast_ragged_ok(level, max_chunk_bytes), nchunks,
-        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
-        d_offsets, s,
-        [&] {
-            return lzh_launch_zstd_dfast_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, t.stride,
-                                                d_csizes, k, base + t.recs, t.rec_stride, s);
-        },
-        [&] {
-            return lzh_launch_pack_ragged(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, t.stride, d_csizes,
-                                          d_offsets, (uint8_t*)d_packed, packed_cap, k, s);
-        });
+    return ragged_compress(zstd_dfast_ragged_ok(level, max_chunk_bytes), true, 1,
+                           zstd_dfast_ragged_temp(nchunks, max_chunk_bytes), d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes,
+                           d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_dfast_ragged(B, level, S, d_csizes, s);
+                           });
 }
 
 size_t lzh_zstd_dfast_ragged_compact_compress_temp_bytes(int level, size_t total_in_bytes, size_t max_chunk_bytes,
@@ -953,22 +884,12 @@ int lzh_zstd_dfast_compress_ragged_compact_async(int level, const void* const* d
                                                  size_t nchunks, size_t max_chunk_bytes, size_t total_in_bytes,
                                                  void* d_packed, size_t packed_cap, uint32_t* d_csizes,
                                                  uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    const CompactTemp t = zstd_dfast_compact_temp(total_in_bytes, max_chunk_bytes, nchunks);
-    const uint32_t k = (uint32_t)nchunks;
-    uint8_t* base = (uint8_t*)d_temp;
-    return ragged_compress(
-        zstd_dfast_ragged_ok(level, max_chunk_bytes), nchunks,
-        d_in_ptrs && d_in_bytes && d_packed && d_csizes && d_offsets && d_temp, 1, t.total, temp_bytes, d_csizes,
-        d_offsets, s,
-        [&] {
-            return lzh_launch_zstd_dfast_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, level, base + t.stage, d_csizes,
-                                                 k, base + t.recs, t.layout(base), s);
-        },
-        [&] {
-            return lzh_launch_pack_compact(d_in_ptrs, d_in_bytes, max_chunk_bytes, base + t.stage, d_csizes, d_offsets,
-                                           (uint8_t*)d_packed, packed_cap, k, t.layout(base), s);
-        });
+    return ragged_compress(zstd_dfast_ragged_ok(level, max_chunk_bytes), true, 1,
+                           zstd_dfast_compact_temp(total_in_bytes, max_chunk_bytes, nchunks), d_in_ptrs, d_in_bytes, nchunks,
+                           max_chunk_bytes, d_packed, packed_cap, d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhCompactSlots& S, hipStream_t s) {
+                               return lzh_launch_zstd_dfast_compact(B, level, S, d_csizes, s);
+                           });
 }
 
 }  // extern "C"

@@ -51,14 +51,32 @@ hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, u
                                           int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
                                           uint8_t* scratch, hipStream_t s);
 size_t lzh_zstd_dfast_scratch_stride(size_t chunk_size);
+// What every ragged compress launcher below is handed (include/lzbench_hip.h 3b .. 3h; api.cpp's ragged_compress
+// forms them, the layouts of temp_layout.h hand out the slots).
+// The batch: chunk i = bytes[i] bytes at ptrs[i] (device arrays of nchunks).  A chunk larger than max_bytes is not
+// processed: csizes[i] = 0, no kernel touches its slots.
+struct LzhBatch {
+    const void* const* ptrs;
+    const uint64_t* bytes;
+    uint64_t max_bytes;
+    uint32_t nchunks;
+};
+// Uniform slots, each sized for max_bytes, slot i for chunk i: staging slots of `stride` bytes; at recs, rec_stride
+// apart, the LZ4 / snappy record slots or the zstd kernels' per-frame scratch areas (null / 0: the call has none);
+// hdr: the per-chunk record counts (null where there are no records).
+struct LzhSlots {
+    uint8_t* stage;
+    uint64_t stride;
+    uint8_t* recs;
+    uint64_t rec_stride;
+    uint32_t* hdr;
+};
+
 // ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip, zstd_ragged_split_hip.hip;
-// include/lzbench_hip.h 3c): chunk i = in_bytes[i] bytes at in_ptrs[i]; staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes)
-// lays them out (fstride: its rec_stride, the scratch areas' distance, at least lzh_zstd_scratch_stride(max_bytes,
-// level)).  Every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 / status[i] = -1 and none of its
-// slots is touched.
-hipError_t lzh_launch_zstd_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                  uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                  uint8_t* scratch, uint64_t fstride, hipStream_t s);
+// include/lzbench_hip.h 3c): staging slots and scratch areas as chunk_temp(LZH_CODEC_ZSTD, nchunks, max_bytes) lays
+// them out (rec_stride at least lzh_zstd_scratch_stride(max_bytes, level)).  Every launch on s.  On the decode side a
+// chunk larger than max_bytes gets status[i] = -1.
+hipError_t lzh_launch_zstd_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
 hipError_t lzh_launch_zstd_decompress_ragged(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                              const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
                                              uint64_t max_bytes, int32_t* status, uint32_t nchunks, hipStream_t s);
@@ -116,8 +134,8 @@ hipError_t lzh_launch_zstd_seq(const uint8_t* packed, uint64_t packed_readable, 
 hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,
                                   uint32_t bpf, int acc, uint8_t* stage, uint64_t stride, uint32_t* bcs, uint32_t* snap,
                                   uint32_t nframes, hipStream_t s);
-// recs / rec_stride / hdr (here and in the snappy and ragged launchers below): the record slots and the per-chunk
-// record counts where the caller's temp layout puts them (ChunkTemp / FrameTemp, temp_layout.h)
+// recs / rec_stride / hdr (here and in the snappy launcher below): the record slots and the per-chunk record counts
+// where the caller's temp layout puts them (ChunkTemp / FrameTemp, temp_layout.h)
 hipError_t lzh_launch_lz4_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
                                 uint64_t rec_stride, uint32_t* hdr, int stage_mask, hipStream_t s,
@@ -139,18 +157,12 @@ void lzh_launch_snappy_emit(K1 k1, K2 k2, K4 k4, K8 k8, uint32_t frags, uint32_t
     else hipLaunchKernelGGL(k8, dim3(nchunks), dim3(64 * W), 0, s, args...);
 }
 
-// ragged batches (ragged_hip.hip, pack_hip.hip): chunk i = in_bytes[i] bytes at in_ptrs[i] (device arrays), every
-// slot sized for max_bytes (chunk_temp(codec, nchunks, max_bytes) of temp_layout.h lays them out); a chunk larger
-// than max_bytes gets csizes[i] = 0
-hipError_t lzh_launch_lz4_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
-                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                 uint64_t rec_stride, uint32_t* hdr, hipStream_t s);
-hipError_t lzh_launch_snappy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                    uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                    uint64_t rec_stride, uint32_t* hdr, hipStream_t s);
-hipError_t lzh_launch_pack_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                  const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
-                                  uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s);
+// ragged batches (ragged_hip.hip, pack_hip.hip): the slots as chunk_temp(codec, nchunks, max_bytes) of temp_layout.h
+// lays them out; the pack launcher reads the staging slots alone
+hipError_t lzh_launch_lz4_ragged(const LzhBatch& B, int acc, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_snappy_ragged(const LzhBatch& B, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_pack_ragged(const LzhBatch& B, const LzhSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                                  uint8_t* packed, uint64_t packed_cap, hipStream_t s);
 // fragments per chunk of a ragged snappy batch (at least 1: the launch grid of a batch of empty chunks)
 uint32_t lzh_snappy_ragged_frags(uint64_t max_bytes);
 // block descriptors (32 bytes each, for lzh_launch_decompress) of a ragged batch: absolute output addresses;
@@ -161,11 +173,9 @@ hipError_t lzh_launch_ragged_desc(const uint64_t* offsets, const uint32_t* csize
 
 // LZ4 ragged batches with a shared dictionary (lz4_dict_hip.hip; include/lzbench_hip.h 3d): dict_bytes in 8 .. 65536,
 // 16 readable bytes after the dictionary; tab: 4096 u32 of temp for LZ4_loadDict's table, built by the call; staging
-// slots of `stride` as above, no records.  Every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 /
-// status[i] = -1.
-hipError_t lzh_launch_lz4_dict(const uint8_t* dict, uint32_t dict_bytes, uint32_t* tab, const void* const* in_ptrs,
-                               const uint64_t* in_bytes, uint64_t max_bytes, int acc, uint8_t* stage, uint64_t stride,
-                               uint32_t* csizes, uint32_t nchunks, hipStream_t s);
+// slots alone, no records.  Every launch on s.  On the decode side a chunk larger than max_bytes gets status[i] = -1.
+hipError_t lzh_launch_lz4_dict(const uint8_t* dict, uint32_t dict_bytes, uint32_t* tab, const LzhBatch& B, int acc,
+                               const LzhSlots& S, uint32_t* csizes, hipStream_t s);
 hipError_t lzh_launch_lz4_dict_decompress(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed,
                                           uint64_t packed_readable, const uint64_t* offsets, const uint32_t* csizes,
                                           void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
@@ -175,9 +185,8 @@ hipError_t lzh_launch_lz4_dict_decompress(const uint8_t* dict, uint32_t dict_byt
 // stage_sz[i] bytes at stage_off[i] of a staging region of stage_cap bytes, its record slot rec_sz[i] bytes at
 // rec_off[i] of a record region of rec_cap bytes (device arrays: nchunks u32, nchunks + 1 u64).
 // lzh_launch_compact_slots fills the four arrays (the slot-size kernel, then lzh_launch_compact_scans: the offset
-// arrays from the size arrays, lzh_launch_scan twice); the other
-// launchers are the ragged ones above with the slots looked up there; hdr: the per-chunk record counts.  A chunk
-// larger than max_bytes, or one with a slot that ends past its region, gets csizes[i] = 0.
+// arrays from the size arrays, lzh_launch_scan twice); the other launchers are the ragged ones above with the slots
+// looked up there.  A chunk larger than max_bytes, or one with a slot that ends past its region, gets csizes[i] = 0.
 // (the arrays are written by lzh_launch_compact_slots alone; every other kernel takes the struct as const)
 struct LzhCompactLayout {
     uint32_t* stage_sz;
@@ -195,19 +204,20 @@ struct LzhZstdSplitCompactTemp {
     void* jobs;          // slots.rec_cap Huffman jobs
     LzhCompactLayout slots;
 };
+// Compact slots, what LzhSlots is to the uniform ones: the staging region, the record region (zstd: the scratch
+// region), the per-chunk record counts (null where there are no records) and the placement.
+struct LzhCompactSlots {
+    uint8_t* stage;
+    uint8_t* recs;
+    uint32_t* hdr;
+    LzhCompactLayout L;
+};
 hipError_t lzh_launch_compact_scans(const LzhCompactLayout& L, uint32_t nchunks, hipStream_t s);
-hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,
-                                    uint32_t nchunks, hipStream_t s);
-hipError_t lzh_launch_lz4_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
-                                  uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
-                                  const LzhCompactLayout& L, hipStream_t s);
-hipError_t lzh_launch_snappy_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                     uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
-                                     const LzhCompactLayout& L, hipStream_t s);
-hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                   const uint8_t* stage, const uint32_t* csizes, const uint64_t* offsets,
-                                   uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, const LzhCompactLayout& L,
-                                   hipStream_t s);
+hipError_t lzh_launch_compact_slots(int codec, const LzhBatch& B, const LzhCompactLayout& L, hipStream_t s);
+hipError_t lzh_launch_lz4_compact(const LzhBatch& B, int acc, const LzhCompactSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_snappy_compact(const LzhBatch& B, const LzhCompactSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_pack_compact(const LzhBatch& B, const LzhCompactSlots& S, const uint32_t* csizes,
+                                   const uint64_t* offsets, uint8_t* packed, uint64_t packed_cap, hipStream_t s);
 
 // the compact layout of a ragged zstd compression (zstd_ragged_compact_hip.hip, zstd_ragged_slots.h): the layout
 // struct above with the record fields carrying the scratch slots -- chunk i's scratch slot is rec_sz[i] bytes at
@@ -219,24 +229,20 @@ hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* i
 struct LzhCompactRegions;   // ragged_slots.h
 LzhCompactRegions lzh_zstd_compact_regions(int level, uint64_t total, uint64_t max_bytes, uint64_t nchunks);
 LzhCompactRegions lzh_zstd_compact_slot(int level, uint64_t n);
-hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                   uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
-                                   const LzhCompactLayout& L, hipStream_t s);
+hipError_t lzh_launch_zstd_compact(const LzhBatch& B, int level, const LzhCompactSlots& S, uint32_t* csizes,
+                                   hipStream_t s);
 
 // ragged zstd level-3 batches (zstd_dfast_ragged_hip.hip, zstd_dfast_slots.h; include/lzbench_hip.h 3e): the
-// launchers of the two layouts above for the double-fast strategy.  lzh_launch_zstd_dfast_ragged: staging slots of
-// `stride` and scratch areas of `fstride` (at least lzh_zstd_dfast_scratch_stride(max(max_bytes, 1))), slot i for
-// chunk i.  lzh_launch_zstd_dfast_compact: the compact layout struct with the record fields carrying the scratch
+// launchers of the two layouts above for the double-fast strategy.  lzh_launch_zstd_dfast_ragged: scratch areas
+// rec_stride apart (at least lzh_zstd_dfast_scratch_stride(max(max_bytes, 1))).  lzh_launch_zstd_dfast_compact: the compact layout struct with the record fields carrying the scratch
 // slots; it fills the four arrays (the level-3 slot-size kernel, then lzh_launch_compact_scans).  Both run one match /
 // entropy pair per block index, ceil(max(max_bytes, 1) / block size) of them, every launch on s; level must be 3.
 // A chunk larger than max_bytes, or (compact) one with a slot that ends past its region, gets csizes[i] = 0.  The two
 // host functions are the slot arithmetic as {staging bytes, scratch bytes}: the two regions, a chunk's two slots.
-hipError_t lzh_launch_zstd_dfast_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                        int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                        uint8_t* scratch, uint64_t fstride, hipStream_t s);
-hipError_t lzh_launch_zstd_dfast_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                         int level, uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
-                                         const LzhCompactLayout& L, hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                        hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_compact(const LzhBatch& B, int level, const LzhCompactSlots& S, uint32_t* csizes,
+                                         hipStream_t s);
 LzhCompactRegions lzh_zstd_dfast_compact_regions(uint64_t total, uint64_t max_bytes, uint64_t nchunks);
 LzhCompactRegions lzh_zstd_dfast_compact_slot(uint64_t n);
 
@@ -246,16 +252,15 @@ LzhCompactRegions lzh_zstd_dfast_compact_slot(uint64_t n);
 // then the frame's own copy of its class's table); lzh_zstd_dict_tables_bytes: the table region (one filled table per
 // (hashLog, minMatch) class a batch can take, a constant bound).  The compress launcher fills the class tables once,
 // then runs the match kernel and the entropy stage of lzh_launch_zstd_entropy_ragged (zstd_ragged_hip.hip), every
-// launch on s.  A chunk larger than max_bytes gets csizes[i] = 0 / status[i] = -1.
+// launch on s (seq_off .. tmp_off: the four areas of a frame's scratch that the entropy stage reads).  On the decode
+// side a chunk larger than max_bytes gets status[i] = -1.
 size_t lzh_zstd_dict_scratch_stride(size_t dict_bytes, size_t max_bytes);
 size_t lzh_zstd_dict_tables_bytes(void);
-hipError_t lzh_launch_zstd_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const void* const* in_ptrs,
-                                const uint64_t* in_bytes, uint64_t max_bytes, int level, uint8_t* stage, uint64_t stride,
-                                uint32_t* csizes, uint32_t nchunks, uint8_t* scratch, uint64_t fstride, hipStream_t s);
-hipError_t lzh_launch_zstd_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                          uint8_t* scratch, uint64_t fstride, uint64_t seq_off, uint64_t lit_off,
-                                          uint64_t att_off, uint64_t tmp_off, hipStream_t s);
+hipError_t lzh_launch_zstd_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const LzhBatch& B, int level,
+                                const LzhSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_zstd_entropy_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                          uint64_t seq_off, uint64_t lit_off, uint64_t att_off, uint64_t tmp_off,
+                                          hipStream_t s);
 hipError_t lzh_launch_zstd_dict_decompress(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed,
                                            uint64_t packed_readable, const uint64_t* offsets, const uint32_t* csizes,
                                            void* const* out_ptrs, const uint64_t* out_bytes, uint64_t max_bytes,
@@ -272,17 +277,14 @@ long lzh_zstd_dict_host_parse(int level, const uint8_t* dict, uint64_t dict_byte
 // any frame of the batch can take); lzh_zstd_dfast_dict_tables_bytes: the table region (one filled pair per (hashLog,
 // chainLog, minMatch) class, a constant bound).  The launcher fills the class tables once, then runs the match kernel
 // and the level-3 entropy stage of lzh_launch_zstd_dfast_entropy_ragged (zstd_dfast_ragged_hip.hip: block 0 of
-// lzh_zstd_dfast_entropy_ragged_kernel alone), every launch on s.  A chunk larger than max_bytes gets csizes[i] = 0.
+// lzh_zstd_dfast_entropy_ragged_kernel alone), every launch on s.
 size_t lzh_zstd_dfast_dict_scratch_stride(size_t dict_bytes, size_t max_bytes);
 size_t lzh_zstd_dfast_dict_tables_bytes(void);
-hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables,
-                                      const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                      uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                      uint8_t* scratch, uint64_t fstride, hipStream_t s);
-hipError_t lzh_launch_zstd_dfast_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                                int level, uint8_t* stage, uint64_t stride, uint32_t* csizes,
-                                                uint32_t nchunks, uint8_t* scratch, uint64_t fstride, uint64_t seq_off,
-                                                uint64_t lit_off, uint64_t att_off, uint64_t tmp_off, hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const LzhBatch& B,
+                                      int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_zstd_dfast_entropy_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                                uint64_t seq_off, uint64_t lit_off, uint64_t att_off, uint64_t tmp_off,
+                                                hipStream_t s);
 // host arithmetic for the debug calls: {windowLog, hashLog, chainLog, minMatch, block size} of ZSTD_getParams(3, n,
 // dict_bytes), and the host walk of one chunk ((ll, ml, offBase) triples and, where events is not null, the counters
 // of zfd::Event added to it; the count, -1: arguments)

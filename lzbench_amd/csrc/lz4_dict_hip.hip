@@ -337,13 +337,12 @@ lzh_lz4_dict_decode_kernel(const uint8_t* dict, uint32_t dict_bytes, const uint8
 
 #include "launch.h"
 
-hipError_t lzh_launch_lz4_dict(const uint8_t* dict, uint32_t dict_bytes, uint32_t* tab, const void* const* in_ptrs,
-                               const uint64_t* in_bytes, uint64_t max_bytes, int acc, uint8_t* stage, uint64_t stride,
-                               uint32_t* csizes, uint32_t nchunks, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_lz4_dict(const uint8_t* dict, uint32_t dict_bytes, uint32_t* tab, const LzhBatch& B, int acc,
+                               const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
     hipLaunchKernelGGL(lzh_lz4_dict_table_kernel, dim3(1), dim3(64), 0, s, dict, dict_bytes, tab);
-    hipLaunchKernelGGL(lzh_lz4_dict_compress_kernel, dim3(nchunks), dim3(64), 0, s, dict, dict_bytes,
-                       (const uint32_t*)tab, in_ptrs, in_bytes, max_bytes, acc, stage, stride, csizes);
+    hipLaunchKernelGGL(lzh_lz4_dict_compress_kernel, dim3(B.nchunks), dim3(64), 0, s, dict, dict_bytes,
+                       (const uint32_t*)tab, B.ptrs, B.bytes, B.max_bytes, acc, S.stage, S.stride, csizes);
     return hipGetLastError();
 }
 

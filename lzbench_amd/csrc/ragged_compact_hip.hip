@@ -159,46 +159,39 @@ hipError_t lzh_launch_compact_scans(const LzhCompactLayout& L, uint32_t nchunks,
     return e != hipSuccess ? e : lzh_launch_scan(L.rec_sz, nchunks, L.rec_off, nullptr, s);
 }
 
-hipError_t lzh_launch_compact_slots(int codec, const uint64_t* in_bytes, uint64_t max_bytes, const LzhCompactLayout& L,
-                                    uint32_t nchunks, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes, max_bytes, codec,
-                       L.stage_sz, L.rec_sz, nchunks);
+hipError_t lzh_launch_compact_slots(int codec, const LzhBatch& B, const LzhCompactLayout& L, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_compact_slots_kernel, dim3((B.nchunks + 255) / 256), dim3(256), 0, s, B.bytes, B.max_bytes,
+                       codec, L.stage_sz, L.rec_sz, B.nchunks);
     const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : lzh_launch_compact_scans(L, nchunks, s);
+    return e != hipSuccess ? e : lzh_launch_compact_scans(L, B.nchunks, s);
 }
 
-hipError_t lzh_launch_lz4_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
-                                  uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
-                                  const LzhCompactLayout& L, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_lz4_parse_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes, acc,
-                       recs, hdr, L);
-    hipLaunchKernelGGL(lzh_lz4_emit_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                       (const uint8_t*)recs, (const uint32_t*)hdr, stage, csizes, L);
+hipError_t lzh_launch_lz4_compact(const LzhBatch& B, int acc, const LzhCompactSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_lz4_parse_compact_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes, acc,
+                       S.recs, S.hdr, S.L);
+    hipLaunchKernelGGL(lzh_lz4_emit_compact_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       (const uint8_t*)S.recs, (const uint32_t*)S.hdr, S.stage, csizes, S.L);
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_snappy_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                     uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* recs, uint32_t* hdr,
-                                     const LzhCompactLayout& L, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    const uint32_t frags = lzh_snappy_ragged_frags(max_bytes);
-    if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lzh_snappy_parse_compact_kernel, dim3(nchunks * frags), dim3(64), 0, s, in_ptrs, in_bytes,
-                       max_bytes, recs, hdr, frags, L);
+hipError_t lzh_launch_snappy_compact(const LzhBatch& B, const LzhCompactSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    const uint32_t frags = lzh_snappy_ragged_frags(B.max_bytes);
+    if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)B.nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lzh_snappy_parse_compact_kernel, dim3(B.nchunks * frags), dim3(64), 0, s, B.ptrs, B.bytes,
+                       B.max_bytes, S.recs, S.hdr, frags, S.L);
     lzh_launch_snappy_emit(lzh_snappy_emit_compact_kernel, lzh_snappy_emit_frag_compact_kernel<2>,
-                           lzh_snappy_emit_frag_compact_kernel<4>, lzh_snappy_emit_frag_compact_kernel<8>, frags, nchunks, s,
-                           in_ptrs, in_bytes, max_bytes, recs, hdr, stage, csizes, frags, L);
+                           lzh_snappy_emit_frag_compact_kernel<4>, lzh_snappy_emit_frag_compact_kernel<8>, frags, B.nchunks,
+                           s, B.ptrs, B.bytes, B.max_bytes, S.recs, S.hdr, S.stage, csizes, frags, S.L);
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_pack_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                   const uint8_t* stage, const uint32_t* csizes, const uint64_t* offsets,
-                                   uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, const LzhCompactLayout& L,
-                                   hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_pack_compact_kernel, dim3(nchunks), dim3(256), 0, s, in_ptrs, in_bytes, max_bytes, stage,
-                       csizes, offsets, packed, packed_cap, L);
+hipError_t lzh_launch_pack_compact(const LzhBatch& B, const LzhCompactSlots& S, const uint32_t* csizes,
+                                   const uint64_t* offsets, uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_pack_compact_kernel, dim3(B.nchunks), dim3(256), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       (const uint8_t*)S.stage, csizes, offsets, packed, packed_cap, S.L);
     return hipGetLastError();
 }

@@ -151,39 +151,34 @@ lzh_ragged_desc_kernel(const uint64_t* offsets, const uint32_t* csizes, void* co
 #include <algorithm>
 #include "launch.h"
 
-hipError_t lzh_launch_lz4_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int acc,
-                                 uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                 uint64_t rs, uint32_t* hdr, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_lz4_parse_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes, acc,
-                       recs, rs, hdr);
-    hipLaunchKernelGGL(lzh_lz4_emit_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                       (const uint8_t*)recs, rs, (const uint32_t*)hdr, stage, stride, csizes);
+hipError_t lzh_launch_lz4_ragged(const LzhBatch& B, int acc, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_lz4_parse_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes, acc,
+                       S.recs, S.rec_stride, S.hdr);
+    hipLaunchKernelGGL(lzh_lz4_emit_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       (const uint8_t*)S.recs, S.rec_stride, (const uint32_t*)S.hdr, S.stage, S.stride, csizes);
     return hipGetLastError();
 }
 
 uint32_t lzh_snappy_ragged_frags(uint64_t max_bytes) { return std::max(1u, lzh_snappy_frags(max_bytes)); }
 
-hipError_t lzh_launch_snappy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                    uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                    uint64_t rs, uint32_t* hdr, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    const uint32_t frags = lzh_snappy_ragged_frags(max_bytes);
-    if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lzh_snappy_parse_ragged_kernel, dim3(nchunks * frags), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                       recs, rs, hdr, frags);
+hipError_t lzh_launch_snappy_ragged(const LzhBatch& B, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    const uint32_t frags = lzh_snappy_ragged_frags(B.max_bytes);
+    if (frags > (uint32_t)sne::kMaxFrags || (uint64_t)B.nchunks * frags > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lzh_snappy_parse_ragged_kernel, dim3(B.nchunks * frags), dim3(64), 0, s, B.ptrs, B.bytes,
+                       B.max_bytes, S.recs, S.rec_stride, S.hdr, frags);
     lzh_launch_snappy_emit(lzh_snappy_emit_ragged_kernel, lzh_snappy_emit_frag_ragged_kernel<2>,
-                           lzh_snappy_emit_frag_ragged_kernel<4>, lzh_snappy_emit_frag_ragged_kernel<8>, frags, nchunks, s,
-                           in_ptrs, in_bytes, max_bytes, recs, rs, hdr, stage, stride, csizes, frags);
+                           lzh_snappy_emit_frag_ragged_kernel<4>, lzh_snappy_emit_frag_ragged_kernel<8>, frags, B.nchunks,
+                           s, B.ptrs, B.bytes, B.max_bytes, S.recs, S.rec_stride, S.hdr, S.stage, S.stride, csizes, frags);
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_pack_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                  const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
-                                  uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_pack_ragged_kernel, dim3(nchunks), dim3(256), 0, s, in_ptrs, in_bytes, max_bytes, stage, stride,
-                       csizes, offsets, packed, packed_cap);
+hipError_t lzh_launch_pack_ragged(const LzhBatch& B, const LzhSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                                  uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_pack_ragged_kernel, dim3(B.nchunks), dim3(256), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       (const uint8_t*)S.stage, S.stride, csizes, offsets, packed, packed_cap);
     return hipGetLastError();
 }
 

@@ -43,6 +43,9 @@ static inline size_t zstd_dfast_scratch_stride(size_t chunk) { return lzh_zstd_d
 struct ChunkTemp {
     bool split;
     size_t stride, rec_stride, stage, recs, hdr, total;
+    LzhSlots slots(uint8_t* base) const {   // (the ragged launchers' bundle; record counts only where there are records)
+        return {base + stage, stride, base + recs, rec_stride, split ? (uint32_t*)(base + hdr) : nullptr};
+    }
 };
 static inline ChunkTemp chunk_temp(int codec, size_t k, size_t chunk) {
     ChunkTemp t = {};
@@ -70,7 +73,10 @@ static inline ChunkTemp chunk_temp(int codec, size_t k, size_t chunk) {
 // chunk_temp, then LZ4_loadDict's table (4096 u32).  No records (the parse emits in-kernel) and no copy of the
 // dictionary: below chunk_temp(LZH_CODEC_LZ4, k, chunk) but for the table.
 static const size_t kLz4DictMax = (size_t)4 << 20;      // largest chunk of the dictionary calls
-struct DictTemp { size_t stride, stage, tab, total; };
+struct DictTemp {
+    size_t stride, stage, tab, total;
+    LzhSlots slots(uint8_t* base) const { return {base + stage, stride, nullptr, 0, nullptr}; }
+};
 static inline DictTemp lz4_dict_temp(size_t k, size_t chunk) {
     DictTemp t;
     TempCursor c;
@@ -86,7 +92,10 @@ static inline DictTemp lz4_dict_temp(size_t k, size_t chunk) {
 // `chunk` bytes and the frame's copy of its class's table, the largest any frame of the batch can take), then the
 // table region: one filled table per (hashLog, minMatch) class, a constant bound (lzh_zstd_dict_tables_bytes).
 static const size_t kZstdDictMax = (size_t)131072;      // largest dictionary and largest chunk of the dictionary calls
-struct ZstdDictTemp { size_t stride, rec_stride, stage, recs, tabs, total; };
+struct ZstdDictTemp {
+    size_t stride, rec_stride, stage, recs, tabs, total;
+    LzhSlots slots(uint8_t* base) const { return {base + stage, stride, base + recs, rec_stride, nullptr}; }
+};
 static inline ZstdDictTemp zstd_dict_temp_with(size_t (*scratch_stride)(size_t, size_t), size_t (*tables_bytes)(void),
                                                size_t dict_bytes, size_t k, size_t chunk) {
     ZstdDictTemp t;
@@ -162,9 +171,10 @@ static inline FrameTemp frame_temp(const FrameGeo& g) {
 struct CompactTemp {
     LzhCompactRegions reg;
     size_t stage, recs, hdr, stage_sz, rec_sz, stage_off, rec_off, total;
-    LzhCompactLayout layout(uint8_t* base) const {
-        return {(uint32_t*)(base + stage_sz), (uint32_t*)(base + rec_sz), (uint64_t*)(base + stage_off),
-                (uint64_t*)(base + rec_off), reg.stage, reg.recs};
+    LzhCompactSlots slots(uint8_t* base) const {   // (hdr 0: a zstd layout, no record counts)
+        return {base + stage, base + recs, hdr ? (uint32_t*)(base + hdr) : nullptr,
+                {(uint32_t*)(base + stage_sz), (uint32_t*)(base + rec_sz), (uint64_t*)(base + stage_off),
+                 (uint64_t*)(base + rec_off), reg.stage, reg.recs}};
     }
 };
 static inline void compact_arrays(CompactTemp& t, TempCursor& c, size_t nchunks, size_t gap) {

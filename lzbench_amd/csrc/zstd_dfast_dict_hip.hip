@@ -159,25 +159,23 @@ long lzh_zstd_dfast_dict_host_parse(int level, const uint8_t* dict, uint64_t dic
     return zfd::host_walk(level, dict, dict_bytes, src, n, seqs, cap, tab.data(), events);
 }
 
-hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables,
-                                      const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                      uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                      uint8_t* scratch, uint64_t fstride, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_dfast_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const LzhBatch& B,
+                                      int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    const uint64_t max_bytes = B.max_bytes;
     if (!zfd::level_ok(level) || dict_bytes < zfd::kDictMin || dict_bytes > zfd::kDictMax || max_bytes > zfd::kChunkMax)
         return hipErrorInvalidValue;
     const zfd::Classes K = zfd::classes_for(level, dict_bytes, max_bytes);
     if (K.count > zfd::kClassCountMax || K.bytes > lzh_zstd_dfast_dict_tables_bytes()) return hipErrorInvalidValue;
-    if (fstride < lzh_zstd_dfast_dict_scratch_stride(dict_bytes, max_bytes)) return hipErrorInvalidValue;
+    if (S.rec_stride < lzh_zstd_dfast_dict_scratch_stride(dict_bytes, max_bytes)) return hipErrorInvalidValue;
     zfd::ClassArg C{};
     zde::fill_class_arg(C, K);
     for (uint32_t i = 0; i < K.count; i++) C.clog[i] = K.clog[i];
     const Layout Lo = layout_for((uint32_t)std::max<uint64_t>(max_bytes, 1), 6);
     const hipError_t e = zde::launch_chain(lzh_zstd_dfast_dict_zero_kernel, lzh_zstd_dfast_dict_table_kernel,
                                            lzh_zstd_dfast_dict_match_kernel, C, K.bytes, zdd::fill_count(dict_bytes), dict,
-                                           dict_bytes, tables, in_ptrs, in_bytes, max_bytes, level, nchunks, scratch,
-                                           fstride, Lo, dfast_dict_pair_cap(dict_bytes, max_bytes), s);
+                                           dict_bytes, tables, B, level, S, Lo,
+                                           dfast_dict_pair_cap(dict_bytes, max_bytes), s);
     if (e != hipSuccess) return e;
-    return lzh_launch_zstd_dfast_entropy_ragged(in_ptrs, in_bytes, max_bytes, level, stage, stride, csizes, nchunks,
-                                                scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, s);
+    return lzh_launch_zstd_dfast_entropy_ragged(B, level, S, csizes, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, s);
 }

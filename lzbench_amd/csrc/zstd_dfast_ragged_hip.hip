@@ -148,21 +148,20 @@ static bool dfast_ragged_geo(uint64_t max_bytes, int level, Layout& Lo, uint32_t
     return true;
 }
 
-hipError_t lzh_launch_zstd_dfast_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                        int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                        uint8_t* scratch, uint64_t fstride, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_dfast_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                        hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
     Layout Lo;
     uint32_t nblocks;
-    if (!dfast_ragged_geo(max_bytes, level, Lo, nblocks)) return hipErrorInvalidValue;
-    if (fstride < lzh_zdslot_scratch_worst(max_bytes)) return hipErrorInvalidValue;
+    if (!dfast_ragged_geo(B.max_bytes, level, Lo, nblocks)) return hipErrorInvalidValue;
+    if (S.rec_stride < lzh_zdslot_scratch_worst(B.max_bytes)) return hipErrorInvalidValue;
     // (every launch on s: a captured call has no parallel branches)
     for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
-        hipLaunchKernelGGL(lzh_zstd_dfast_match_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                           level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off);
-        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes,
-                           max_bytes, level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off,
-                           stage, stride, csizes);
+        hipLaunchKernelGGL(lzh_zstd_dfast_match_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, S.rec_stride, Lo.seq_off, Lo.lit_off, Lo.tab_off);
+        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, S.rec_stride, Lo.seq_off, Lo.lit_off, Lo.att_off,
+                           Lo.tmp_off, S.stage, S.stride, csizes);
     }
     return hipGetLastError();
 }
@@ -170,33 +169,31 @@ hipError_t lzh_launch_zstd_dfast_ragged(const void* const* in_ptrs, const uint64
 // The entropy stage of block 0 alone, for a caller with a match kernel of its own that writes this kernel's scratch
 // layout (zstd_dfast_dict_hip.hip): frames of one block, the parameters the body reads (block size, literal
 // compression) being those of the plain call.
-hipError_t lzh_launch_zstd_dfast_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                                int level, uint8_t* stage, uint64_t stride, uint32_t* csizes,
-                                                uint32_t nchunks, uint8_t* scratch, uint64_t fstride, uint64_t seq_off,
-                                                uint64_t lit_off, uint64_t att_off, uint64_t tmp_off, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_zstd_dfast_entropy_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                       level, 0, scratch, fstride, seq_off, lit_off, att_off, tmp_off, stage, stride, csizes);
+hipError_t lzh_launch_zstd_dfast_entropy_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                                uint64_t seq_off, uint64_t lit_off, uint64_t att_off, uint64_t tmp_off,
+                                                hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_zstd_dfast_entropy_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       level, 0, S.recs, S.rec_stride, seq_off, lit_off, att_off, tmp_off, S.stage, S.stride, csizes);
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_zstd_dfast_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                         int level, uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
-                                         const LzhCompactLayout& L, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_dfast_compact(const LzhBatch& B, int level, const LzhCompactSlots& S, uint32_t* csizes,
+                                         hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
     Layout Lo;
     uint32_t nblocks;
-    if (!dfast_ragged_geo(max_bytes, level, Lo, nblocks)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lzh_zstd_dfast_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes,
-                       max_bytes, L.stage_sz, L.rec_sz, nchunks);
+    if (!dfast_ragged_geo(B.max_bytes, level, Lo, nblocks)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lzh_zstd_dfast_compact_slots_kernel, dim3((B.nchunks + 255) / 256), dim3(256), 0, s, B.bytes,
+                       B.max_bytes, S.L.stage_sz, S.L.rec_sz, B.nchunks);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = lzh_launch_compact_scans(L, nchunks, s);
+    if (e == hipSuccess) e = lzh_launch_compact_scans(S.L, B.nchunks, s);
     if (e != hipSuccess) return e;
     for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
-        hipLaunchKernelGGL(lzh_zstd_dfast_match_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes,
-                           max_bytes, level, (int)k, scratch, L);
-        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes,
-                           max_bytes, level, (int)k, scratch, stage, csizes, L);
+        hipLaunchKernelGGL(lzh_zstd_dfast_match_compact_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, S.L);
+        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_compact_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, S.stage, csizes, S.L);
     }
     return hipGetLastError();
 }

@@ -90,6 +90,7 @@ inline void fill_class_arg(Arg& C, const Classes& K) {
 #ifdef __HIPCC__
 // ------------------------------------------------------------------------- device side: one wave per chunk
 #include "zstdc.h"
+#include "launch.h"
 
 namespace zde {
 
@@ -185,15 +186,14 @@ __device__ __forceinline__ void close_frame(rsrc_t hdr, const Bytes& in, zc::Seq
 // zeroed, the dictionary's fill of every class (none for a dictionary too short to index), one wave per chunk.
 template <class ZeroK, class TableK, class MatchK, class Arg>
 inline hipError_t launch_chain(ZeroK zero, TableK table, MatchK match, const Arg& C, uint32_t tables_bytes, uint32_t nfill,
-                               const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const void* const* in_ptrs,
-                               const uint64_t* in_bytes, uint64_t max_bytes, int level, uint32_t nchunks, uint8_t* scratch,
-                               uint64_t fstride, const zc::Layout& Lo, uint32_t tab_cap, hipStream_t s) {
+                               const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const LzhBatch& B, int level,
+                               const LzhSlots& S, const zc::Layout& Lo, uint32_t tab_cap, hipStream_t s) {
     hipLaunchKernelGGL(zero, dim3((tables_bytes / 4 + 255) / 256), dim3(256), 0, s, (uint32_t*)tables, tables_bytes / 4);
     if (nfill)
         hipLaunchKernelGGL(table, dim3((nfill + 255) / 256, C.count), dim3(256), 0, s, dict, dict_bytes, nfill,
                            (uint32_t*)tables, C);
-    hipLaunchKernelGGL(match, dim3(nchunks), dim3(64), 0, s, dict, dict_bytes, (const uint8_t*)tables, C, in_ptrs,
-                       in_bytes, max_bytes, level, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off, tab_cap);
+    hipLaunchKernelGGL(match, dim3(B.nchunks), dim3(64), 0, s, dict, dict_bytes, (const uint8_t*)tables, C, B.ptrs,
+                       B.bytes, B.max_bytes, level, S.recs, S.rec_stride, Lo.seq_off, Lo.lit_off, Lo.tab_off, tab_cap);
     return hipGetLastError();
 }
 

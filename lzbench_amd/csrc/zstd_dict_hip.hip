@@ -195,25 +195,24 @@ long lzh_zstd_dict_host_parse(int level, const uint8_t* dict, uint64_t dict_byte
     return zdd::host_walk(level, dict, dict_bytes, src, n, seqs, cap, tab.data());
 }
 
-hipError_t lzh_launch_zstd_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const void* const* in_ptrs,
-                                const uint64_t* in_bytes, uint64_t max_bytes, int level, uint8_t* stage, uint64_t stride,
-                                uint32_t* csizes, uint32_t nchunks, uint8_t* scratch, uint64_t fstride, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_dict(const uint8_t* dict, uint32_t dict_bytes, uint8_t* tables, const LzhBatch& B, int level,
+                                const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    const uint64_t max_bytes = B.max_bytes;
     if (!zdd::level_ok(level) || dict_bytes < zdd::kDictMin || dict_bytes > zdd::kDictMax || max_bytes > zdd::kChunkMax)
         return hipErrorInvalidValue;
     const zdd::Classes K = zdd::classes_for(level, dict_bytes, max_bytes);
     if (K.count > 12 || K.bytes > lzh_zstd_dict_tables_bytes()) return hipErrorInvalidValue;
-    if (fstride < lzh_zstd_dict_scratch_stride(dict_bytes, max_bytes)) return hipErrorInvalidValue;
+    if (S.rec_stride < lzh_zstd_dict_scratch_stride(dict_bytes, max_bytes)) return hipErrorInvalidValue;
     zdd::ClassArg C{};
     zde::fill_class_arg(C, K);
     const uint32_t hcap = dict_hlog_cap(dict_bytes, max_bytes);
     const Layout Lo = layout_for((uint32_t)std::max<uint64_t>(max_bytes, 1), hcap);
     const hipError_t e = zde::launch_chain(lzh_zstd_dict_zero_kernel, lzh_zstd_dict_table_kernel, lzh_zstd_dict_match_kernel,
-                                           C, K.bytes, zdd::fill_count(dict_bytes), dict, dict_bytes, tables, in_ptrs,
-                                           in_bytes, max_bytes, level, nchunks, scratch, fstride, Lo, 4u << hcap, s);
+                                           C, K.bytes, zdd::fill_count(dict_bytes), dict, dict_bytes, tables, B, level, S,
+                                           Lo, 4u << hcap, s);
     if (e != hipSuccess) return e;
-    return lzh_launch_zstd_entropy_ragged(in_ptrs, in_bytes, max_bytes, level, stage, stride, csizes, nchunks, scratch,
-                                          fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, s);
+    return lzh_launch_zstd_entropy_ragged(B, level, S, csizes, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, s);
 }
 
 hipError_t lzh_launch_zstd_dict_decompress(const uint8_t* dict, uint32_t dict_bytes, const uint8_t* packed,

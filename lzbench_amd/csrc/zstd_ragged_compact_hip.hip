@@ -93,28 +93,27 @@ LzhCompactRegions lzh_zstd_compact_slot(int level, uint64_t n) {
     return {lzh_zslot_stage_bytes(n), lzh_zslot_scratch_bytes(level, n)};
 }
 
-hipError_t lzh_launch_zstd_compact(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                   uint8_t* stage, uint32_t* csizes, uint32_t nchunks, uint8_t* scratch,
-                                   const LzhCompactLayout& L, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_compact(const LzhBatch& B, int level, const LzhCompactSlots& S, uint32_t* csizes,
+                                   hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
     // (the block count and the table's LDS of a batch of empty chunks are those of 1-byte chunks, as in
     // lzh_launch_zstd_ragged)
-    const uint64_t geo = std::max<uint64_t>(max_bytes, 1);
+    const uint64_t geo = std::max<uint64_t>(B.max_bytes, 1);
     const ZParams PF = params_for(level, geo);
     if (!PF.ok) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lzh_zstd_compact_slots_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, in_bytes, max_bytes,
-                       level, L.stage_sz, L.rec_sz, nchunks);
+    hipLaunchKernelGGL(lzh_zstd_compact_slots_kernel, dim3((B.nchunks + 255) / 256), dim3(256), 0, s, B.bytes,
+                       B.max_bytes, level, S.L.stage_sz, S.L.rec_sz, B.nchunks);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = lzh_launch_compact_scans(L, nchunks, s);
+    if (e == hipSuccess) e = lzh_launch_compact_scans(S.L, B.nchunks, s);
     if (e != hipSuccess) return e;
     const uint32_t nblocks = (uint32_t)((geo + PF.bsize - 1) / PF.bsize);
     const uint32_t lds_tab = lzh_zstd_lds_table(level, geo);
     // (every launch on s, as lzh_launch_zstd_ragged: a captured call has no parallel branches)
     for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
-        hipLaunchKernelGGL(lzh_zstd_match_compact_kernel, dim3(nchunks), dim3(64), lds_tab, s, in_ptrs, in_bytes,
-                           max_bytes, level, (int)k, scratch, lds_tab, L);
-        hipLaunchKernelGGL(lzh_zstd_entropy_compact_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                           level, (int)k, scratch, stage, csizes, L);
+        hipLaunchKernelGGL(lzh_zstd_match_compact_kernel, dim3(B.nchunks), dim3(64), lds_tab, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, lds_tab, S.L);
+        hipLaunchKernelGGL(lzh_zstd_entropy_compact_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                           level, (int)k, S.recs, S.stage, csizes, S.L);
     }
     return hipGetLastError();
 }

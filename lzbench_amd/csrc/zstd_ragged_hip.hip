@@ -59,27 +59,25 @@ lzh_zstd_entropy_ragged_kernel(const void* const* in_ptrs, const uint64_t* in_by
 #include <algorithm>
 #include "launch.h"
 
-hipError_t lzh_launch_zstd_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes, int level,
-                                  uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                  uint8_t* scratch, uint64_t fstride, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
+hipError_t lzh_launch_zstd_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
     // (the slots of a batch of empty chunks are those of 1-byte chunks, as api.cpp sizes them: size 0 is
     // ZSTD_getParams' "unknown size")
-    const uint64_t geo = std::max<uint64_t>(max_bytes, 1);
+    const uint64_t geo = std::max<uint64_t>(B.max_bytes, 1);
     const ZParams PF = params_for(level, geo);
     if (!PF.ok) return hipErrorInvalidValue;
-    if (fstride < lzh_zstd_scratch_stride(geo, level)) return hipErrorInvalidValue;
+    if (S.rec_stride < lzh_zstd_scratch_stride(geo, level)) return hipErrorInvalidValue;
     const Layout Lo = layout_for(PF.bsize, 16);   // offsets below tab_off do not depend on hlog
     const uint32_t nblocks = (uint32_t)((geo + PF.bsize - 1) / PF.bsize);
     const uint32_t lds_tab = lzh_zstd_lds_table(level, geo);
     // (the uniform launcher's plain loop; its side-stream split of single-block frames is left out on purpose:
     // every launch stays on s, so a captured call has no parallel branches)
     for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
-        hipLaunchKernelGGL(lzh_zstd_match_ragged_kernel, dim3(nchunks), dim3(64), lds_tab, s, in_ptrs, in_bytes, max_bytes,
-                           level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off, lds_tab);
-        hipLaunchKernelGGL(lzh_zstd_entropy_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes,
-                           level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, stage, stride,
-                           csizes);
+        hipLaunchKernelGGL(lzh_zstd_match_ragged_kernel, dim3(B.nchunks), dim3(64), lds_tab, s, B.ptrs, B.bytes,
+                           B.max_bytes, level, (int)k, S.recs, S.rec_stride, Lo.seq_off, Lo.lit_off, Lo.tab_off, lds_tab);
+        hipLaunchKernelGGL(lzh_zstd_entropy_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                           level, (int)k, S.recs, S.rec_stride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off, S.stage,
+                           S.stride, csizes);
     }
     return hipGetLastError();
 }
@@ -87,12 +85,11 @@ hipError_t lzh_launch_zstd_ragged(const void* const* in_ptrs, const uint64_t* in
 // The entropy stage of block 0 alone, for a caller with a match kernel of its own that writes this kernel's scratch
 // layout (zstd_dict_hip.hip): frames of one block, the parameters the body reads (block size, literal compression)
 // being those of the plain call.
-hipError_t lzh_launch_zstd_entropy_ragged(const void* const* in_ptrs, const uint64_t* in_bytes, uint64_t max_bytes,
-                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                          uint8_t* scratch, uint64_t fstride, uint64_t seq_off, uint64_t lit_off,
-                                          uint64_t att_off, uint64_t tmp_off, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_zstd_entropy_ragged_kernel, dim3(nchunks), dim3(64), 0, s, in_ptrs, in_bytes, max_bytes, level,
-                       0, scratch, fstride, seq_off, lit_off, att_off, tmp_off, stage, stride, csizes);
+hipError_t lzh_launch_zstd_entropy_ragged(const LzhBatch& B, int level, const LzhSlots& S, uint32_t* csizes,
+                                          uint64_t seq_off, uint64_t lit_off, uint64_t att_off, uint64_t tmp_off,
+                                          hipStream_t s) {
+    if (B.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_zstd_entropy_ragged_kernel, dim3(B.nchunks), dim3(64), 0, s, B.ptrs, B.bytes, B.max_bytes,
+                       level, 0, S.recs, S.rec_stride, seq_off, lit_off, att_off, tmp_off, S.stage, S.stride, csizes);
     return hipGetLastError();
 }

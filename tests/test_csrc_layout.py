@@ -159,6 +159,31 @@ def test_two_view_counts_are_defined_once():
         assert [f for f, s in _sources().items() if re.search(r"^__device__ .*\b%s\(" % name, s, re.M)] == [DICT_ENV]
 
 
+# The ragged compress calls: one batch struct and one slots struct per layout from api.cpp's ragged_compress to the
+# launchers (launch.h LzhBatch, LzhSlots, LzhCompactSlots).
+def _code(text):
+    """the text without its // comments"""
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def test_launch_h_names_the_batch_arrays_in_the_batch_struct_alone():
+    code = _code(_sources()["launch.h"])
+    assert re.search(r"struct LzhBatch \{\s*const void\* const\* ptrs;\s*const uint64_t\* bytes;", code)
+    for name in ("in_ptrs", "in_bytes"):
+        assert not re.search(r"\b%s\b" % name, code), name
+    assert len(re.findall(r"\bconst void\* const\*", code)) == 1   # (the struct's field: no launcher spells it out)
+
+
+def test_api_packs_and_tests_its_pointers_in_one_place():
+    code = _code(_sources()["api.cpp"])
+    for launcher in ("lzh_launch_pack_ragged(", "lzh_launch_pack_compact("):
+        assert code.count(launcher) == 1, launcher
+    six = r"d_in_ptrs\s*&&\s*d_in_bytes\s*&&\s*d_packed\s*&&\s*d_csizes\s*&&\s*d_offsets\s*&&\s*d_temp\b"
+    assert len(re.findall(six, code)) == 1
+    # (and no entry point tests a part of it on its own)
+    assert len(re.findall(r"d_in_ptrs\s*&&", code)) == 1
+
+
 @pytest.mark.parametrize("header", COMPRESS_HEADERS + (DICT_ENV,))
 def test_compress_header_compiles_when_included_first(header, tmp_path):
     r = _syntax_check(tmp_path, '#include "%s"\n' % header)
