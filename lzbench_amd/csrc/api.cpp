@@ -119,66 +119,97 @@ size_t lzh_decompress_temp_bytes(int codec, size_t n, size_t chunk_size) {
     return decode_temp(decode_codec(codec), n, chunk_size).total;
 }
 
-int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* d_in, size_t n, size_t in_readable,
-                              size_t chunk_size, void* d_stage, uint32_t* d_csizes, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (!chunk_size || !d_stage || !d_csizes || (n && !d_in)) return LZH_EARG;
+// ---- the uniform compress calls: one input buffer cut at chunk_size ----
+// chunk counts and sizes the kernels hold in 32 bits
+static bool fits_u32(size_t k, size_t chunk_size) { return k <= 0xffffffffu && chunk_size <= 0x7fff0000u; }
+
+// the codec takes the level, and n bytes in chunks of chunk_size
+static bool uniform_ok(int codec, int level, size_t n, size_t chunk_size) {
+    if (!fits_u32(lzh_num_chunks(n, chunk_size), chunk_size)) return false;
+    if (codec == LZH_CODEC_LZ4 || codec == LZH_CODEC_SNAPPY) return true;
+    if (is_frame(codec)) return frame_level_ok(codec, level);
+    if (codec == LZH_CODEC_ZSTD) return lzh_zstd_level_ok(level, chunk_size) != 0;
+    return codec == LZH_CODEC_ZSTD_DFAST && level == 3 && chunk_size <= kLz4SplitMax;
+}
+
+// What a uniform compress call hands its launchers, formed once, after the argument checks (uniform_ok): the input
+// and the slots of the call's layout in temp -- chunk_temp, where F.blocks alone is set; for a framed codec frame_temp
+// of the level's geometry, where I's chunks are the blocks.
+struct UniformCall {
+    LzhInput I;
+    LzhFrameSlots F;
+    bool split;   // LZ4 / snappy: parse -> records -> emit
+};
+static UniformCall uniform_call(int codec, int level, const void* d_in, size_t n, size_t in_readable, size_t chunk_size,
+                                const void* temp) {
+    const uint8_t* in = (const uint8_t*)d_in;
+    uint8_t* base = (uint8_t*)temp;   // (const in lzh_compress_finish_async, which only reads the staging slots)
+    if (is_frame(codec)) {
+        const FrameGeo g = frame_geo(frame_block_bytes(codec, level), n, chunk_size);
+        return {{in, n, in_readable, g.bs, (uint32_t)g.nblocks, g.F, g.bpf, (uint32_t)g.nframes}, frame_temp(g).slots(base),
+                true};
+    }
     const size_t k = lzh_num_chunks(n, chunk_size);
-    if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
-    uint8_t* base = (uint8_t*)d_stage;
+    const ChunkTemp t = chunk_temp(codec, k, chunk_size);
+    return {{in, n, in_readable, chunk_size, (uint32_t)k, 0, 1, (uint32_t)k}, {t.slots(base), nullptr, nullptr},
+            t.split};
+}
+
+// the compress kernels of the call; stage_mask bit 0: parse / the whole compression, bit 1: emit, frame sizes
+static int uniform_kernels(int codec, int level, int stage_mask, const UniformCall& c, uint32_t* d_csizes, hipStream_t s) {
+    const LzhInput& I = c.I;
+    const LzhSlots& S = c.F.blocks;
     Range range("lzh:compress_kernel");
     if (codec == LZH_CODEC_LZ4) {
-        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
-        if (t.split) {
-            LZH_CHECK(lzh_launch_lz4_split((const uint8_t*)d_in, n, in_readable, chunk_size, level < 1 ? 1 : level,
-                                           base + t.stage, t.stride, d_csizes, (uint32_t)k, base + t.recs, t.rec_stride,
-                                           (uint32_t*)(base + t.hdr), stage_mask, s));
-        } else if (stage_mask & 1) {
-            LZH_CHECK(lzh_launch_lz4_compress_v2((const uint8_t*)d_in, n, in_readable, chunk_size, level < 1 ? 1 : level,
-                                                 base + t.stage, t.stride, d_csizes, (uint32_t)k, s));
-        }
+        const int acc = level < 1 ? 1 : level;
+        if (c.split) LZH_CHECK(lzh_launch_lz4_split(I, acc, S, d_csizes, stage_mask, s));
+        else if (stage_mask & 1) LZH_CHECK(lzh_launch_lz4_compress_v2(I, acc, S, d_csizes, s));
     } else if (codec == LZH_CODEC_SNAPPY) {
-        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
-        if (t.split) {
-            LZH_CHECK(lzh_launch_snappy_split((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage, t.stride,
-                                              d_csizes, (uint32_t)k, base + t.recs, t.rec_stride,
-                                              (uint32_t*)(base + t.hdr), stage_mask, s));
-        } else if (stage_mask & 1) {
-            LZH_CHECK(lzh_launch_snappy_compress_v2((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage,
-                                                    t.stride, d_csizes, (uint32_t)k, s));
-        }
-    } else if (is_frame(codec)) {
-        // (d_stage = the whole compression temp of a framed layout; d_csizes = frame sizes)
-        if (!frame_level_ok(codec, level)) return LZH_EARG;
-        const FrameGeo g = frame_geo(frame_block_bytes(codec, level), n, chunk_size);
-        const FrameTemp t = frame_temp(g);
-        uint32_t* bcs = (uint32_t*)(base + t.bcs);
+        if (c.split) LZH_CHECK(lzh_launch_snappy_split(I, S, d_csizes, stage_mask, s));
+        else if (stage_mask & 1) LZH_CHECK(lzh_launch_snappy_compress_v2(I, S, d_csizes, s));
+    } else if (is_frame(codec)) {   // blocks -> frame sizes (d_csizes)
         const int acc = codec == LZH_CODEC_LZ4F ? std::max(1, (level >> 8) & 0xff) : 1;
         if (codec == LZH_CODEC_LZ4F && (level & LZH_LZ4F_LINKED)) {
             // linked blocks: one wave per frame walks its blocks in order (the records area holds the
             // per-frame table snapshots: 16 KiB per frame)
-            if (stage_mask & 1)
-                LZH_CHECK(lzh_launch_lz4f_linked((const uint8_t*)d_in, n, in_readable, g.F, g.bs, g.bpf, acc,
-                                                 base + t.stage, t.stride, bcs, (uint32_t*)(base + t.recs),
-                                                 (uint32_t)g.nframes, s));
+            if (stage_mask & 1) LZH_CHECK(lzh_launch_lz4f_linked(I, acc, c.F, s));
         } else {
-            LZH_CHECK(lzh_launch_lz4_split((const uint8_t*)d_in, n, in_readable, g.bs, acc, base + t.stage, t.stride, bcs,
-                                           (uint32_t)g.nblocks, base + t.recs, t.rec_stride, (uint32_t*)(base + t.hdr),
-                                           stage_mask, s, g.F, g.bpf));
+            LZH_CHECK(lzh_launch_lz4_split(I, acc, S, c.F.bcs, stage_mask, s));
         }
-        if (stage_mask & 2)
-            LZH_CHECK(lzh_launch_frame_sizes(codec, level, n, g.F, g.bs, g.bpf, bcs, (uint32_t*)(base + t.rel), d_csizes,
-                                             (uint32_t)g.nframes, s));
+        if (stage_mask & 2) LZH_CHECK(lzh_launch_frame_sizes(I, codec, level, c.F.bcs, c.F.rel, d_csizes, s));
     } else if (codec == LZH_CODEC_ZSTD) {
-        if (!lzh_zstd_level_ok(level, chunk_size)) return LZH_EARG;
-        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
-        if (stage_mask & 1)
-            LZH_CHECK(lzh_launch_zstd_compress((const uint8_t*)d_in, n, in_readable, chunk_size, level, base + t.stage,
-                                               t.stride, d_csizes, (uint32_t)k, base + t.recs, s));
-    } else {
-        return LZH_EARG;
+        if (stage_mask & 1) LZH_CHECK(lzh_launch_zstd_compress(I, level, S, d_csizes, s));
+    } else {   // LZH_CODEC_ZSTD_DFAST: match + entropy per block index, every launch on s
+        LZH_CHECK(lzh_launch_zstd_dfast_compress(I, level, S, d_csizes, s));
     }
     return LZH_OK;
+}
+
+// sizes -> offsets -> the chunks (frames) back to back in d_packed
+static int uniform_scan_pack(int codec, int level, const UniformCall& c, const uint32_t* d_csizes, uint64_t* d_offsets,
+                             void* d_packed, size_t packed_cap, hipStream_t s) {
+    Range range("lzh:scan_pack");
+    LZH_CHECK(lzh_launch_scan(d_csizes, c.I.nframes, d_offsets, nullptr, s));
+    if (is_frame(codec)) {
+        LZH_CHECK(lzh_launch_frame_pack(c.I, codec, level, c.F, d_csizes, d_offsets, (uint8_t*)d_packed, s));
+    } else if (codec == LZH_CODEC_ZSTD_DFAST && c.I.n_total == 0) {
+        // (the pack kernel looks chunks up in the input and finds none in an empty one: the one frame of an empty
+        // input -- magic, descriptor, a content size of 0, an empty last raw block -- is copied as it is)
+        const size_t kEmptyFrame = 4 + 1 + 1 + 3;
+        LZH_CHECK(lzh_launch_memcpy(c.F.blocks.stage, d_packed, kEmptyFrame, s));
+    } else {
+        LZH_CHECK(lzh_launch_pack(c.I, c.F.blocks, d_csizes, d_offsets, (uint8_t*)d_packed, packed_cap, s));
+    }
+    return LZH_OK;
+}
+
+// (d_stage = the whole compression temp; framed layouts: d_csizes = frame sizes)
+int lzh_compress_kernel_stage(int codec, int level, int stage_mask, const void* d_in, size_t n, size_t in_readable,
+                              size_t chunk_size, void* d_stage, uint32_t* d_csizes, void* hip_stream) {
+    if (!chunk_size || !d_stage || !d_csizes || (n && !d_in)) return LZH_EARG;
+    if (codec == LZH_CODEC_ZSTD_DFAST || !uniform_ok(codec, level, n, chunk_size)) return LZH_EARG;
+    return uniform_kernels(codec, level, stage_mask, uniform_call(codec, level, d_in, n, in_readable, chunk_size, d_stage),
+                           d_csizes, (hipStream_t)hip_stream);
 }
 
 int lzh_compress_kernel_only(int codec, int level, const void* d_in, size_t n, size_t in_readable,
@@ -198,8 +229,8 @@ int lzh_compress_async(int codec, int level, const void* d_in, size_t n, size_t 
     hipStream_t s = (hipStream_t)hip_stream;
     if (!chunk_size || !d_packed || !d_csizes || !d_offsets || (n && !d_in)) return LZH_EARG;
     if (in_readable < n) return LZH_EARG;
-    const size_t k = lzh_num_chunks(n, chunk_size);
     if (codec == LZH_CODEC_MEMCPY) {
+        const size_t k = lzh_num_chunks(n, chunk_size);
         if (packed_cap < n) return LZH_ESPACE;
         if (n == 0) return LZH_OK;
         hipLaunchKernelGGL(lzh_fill_raw_sizes, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, d_csizes,
@@ -211,66 +242,21 @@ int lzh_compress_async(int codec, int level, const void* d_in, size_t n, size_t 
     }
     if (temp_bytes < lzh_compress_temp_bytes(codec, n, chunk_size) || !d_temp) return LZH_ESPACE;
     if (packed_cap < lzh_max_packed_bytes(codec, n, chunk_size)) return LZH_ESPACE;
-    if (is_frame(codec)) {   // blocks -> frame sizes -> frame offsets -> frames
-        if (!frame_level_ok(codec, level)) return LZH_EARG;
-        if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
-        int rc = lzh_compress_kernel_stage(codec, level, 3, d_in, n, in_readable, chunk_size, d_temp, d_csizes, hip_stream);
-        if (rc) return rc;
-        const FrameGeo g = frame_geo(frame_block_bytes(codec, level), n, chunk_size);
-        const FrameTemp t = frame_temp(g);
-        const uint8_t* base = (const uint8_t*)d_temp;
-        Range range("lzh:scan_pack");
-        LZH_CHECK(lzh_launch_scan(d_csizes, k, d_offsets, nullptr, s));
-        LZH_CHECK(lzh_launch_frame_pack(codec, level, (const uint8_t*)d_in, n, in_readable, g.F, g.bs, g.bpf,
-                                        base + t.stage, t.stride, (const uint32_t*)(base + t.bcs),
-                                        (const uint32_t*)(base + t.rel), d_csizes, d_offsets, (uint8_t*)d_packed,
-                                        (uint32_t)g.nblocks, (uint32_t)g.nframes, s));
-        return LZH_OK;
-    }
-    if (codec == LZH_CODEC_ZSTD_DFAST) {   // match + entropy per block index -> scan -> pack, every launch on s
-        if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
-        if (level != 3 || chunk_size > kLz4SplitMax) return LZH_EARG;
-        const ChunkTemp t = chunk_temp(codec, k, chunk_size);
-        uint8_t* base = (uint8_t*)d_temp;
-        {
-            Range range("lzh:compress_kernel");
-            LZH_CHECK(lzh_launch_zstd_dfast_compress((const uint8_t*)d_in, n, in_readable, chunk_size, level,
-                                                     base + t.stage, t.stride, d_csizes, (uint32_t)k, base + t.recs, s));
-        }
-        Range range("lzh:scan_pack");
-        LZH_CHECK(lzh_launch_scan(d_csizes, k, d_offsets, nullptr, s));
-        if (n == 0) {
-            // (the pack kernel looks chunks up in the input and finds none in an empty one: the one frame of an empty
-            // input -- magic, descriptor, a content size of 0, an empty last raw block -- is copied as it is)
-            const size_t kEmptyFrame = 4 + 1 + 1 + 3;
-            LZH_CHECK(lzh_launch_memcpy(base + t.stage, d_packed, kEmptyFrame, s));
-            return LZH_OK;
-        }
-        LZH_CHECK(lzh_launch_pack((const uint8_t*)d_in, n, in_readable, chunk_size, base + t.stage, t.stride, d_csizes,
-                                  d_offsets, (uint8_t*)d_packed, packed_cap, (uint32_t)k, s));
-        return LZH_OK;
-    }
-    int rc = lzh_compress_kernel_only(codec, level, d_in, n, in_readable, chunk_size, d_temp, d_csizes, hip_stream);
-    if (rc) return rc;
-    return lzh_compress_finish_async(codec, d_in, n, in_readable, chunk_size, d_temp, d_csizes, d_packed, packed_cap,
-                                     d_offsets, hip_stream);
+    if (!uniform_ok(codec, level, n, chunk_size)) return LZH_EARG;
+    const UniformCall c = uniform_call(codec, level, d_in, n, in_readable, chunk_size, d_temp);
+    const int rc = uniform_kernels(codec, level, 3, c, d_csizes, s);
+    return rc ? rc : uniform_scan_pack(codec, level, c, d_csizes, d_offsets, d_packed, packed_cap, s);
 }
 
 int lzh_compress_finish_async(int codec, const void* d_in, size_t n, size_t in_readable, size_t chunk_size,
                               const void* d_stage, const uint32_t* d_csizes, void* d_packed, size_t packed_cap,
                               uint64_t* d_offsets, void* hip_stream) {
-    hipStream_t s = (hipStream_t)hip_stream;
     if (!chunk_size || !d_stage || !d_csizes || !d_packed || !d_offsets) return LZH_EARG;
     if (codec != LZH_CODEC_LZ4 && codec != LZH_CODEC_SNAPPY && codec != LZH_CODEC_ZSTD) return LZH_EARG;
     // the sizes are only known on the device: the worst case must fit (no silent truncation)
     if (packed_cap < lzh_max_packed_bytes(codec, n, chunk_size)) return LZH_ESPACE;
-    const size_t k = lzh_num_chunks(n, chunk_size);
-    const ChunkTemp t = chunk_temp(codec, k, chunk_size);
-    Range range("lzh:scan_pack");
-    LZH_CHECK(lzh_launch_scan(d_csizes, k, d_offsets, nullptr, s));
-    LZH_CHECK(lzh_launch_pack((const uint8_t*)d_in, n, in_readable, chunk_size, (const uint8_t*)d_stage + t.stage, t.stride,
-                              d_csizes, d_offsets, (uint8_t*)d_packed, packed_cap, (uint32_t)k, s));
-    return LZH_OK;
+    return uniform_scan_pack(codec, 0, uniform_call(codec, 0, d_in, n, in_readable, chunk_size, d_stage), d_csizes,
+                             d_offsets, d_packed, packed_cap, (hipStream_t)hip_stream);
 }
 
 int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
@@ -297,7 +283,7 @@ int lzh_decompress_async(int codec, const void* d_packed, size_t packed_readable
         offs = (const uint64_t*)(base + t.scan);
     }
     if (is_frame(codec)) {   // frame headers -> block descriptors -> blocks -> frame checks
-        if (k > 0xffffffffu || chunk_size > 0x7fff0000u) return LZH_EARG;
+        if (!fits_u32(k, chunk_size)) return LZH_EARG;
         const uint32_t mb = frame_maxbpf(codec, chunk_size);
         const size_t nd = k * mb;
         void* desc = base + t.desc;

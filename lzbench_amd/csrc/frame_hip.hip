@@ -368,21 +368,19 @@ lzh_frame_finish_kernel(int codec, const uint8_t* packed, const uint64_t* offset
 }
 
 #include "launch.h"
-hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
-                                  const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s) {
-    if (!nframes) return hipSuccess;
-    hipLaunchKernelGGL(lzh_frame_size_kernel, dim3((nframes + 255) / 256), dim3(256), 0, s, codec, params, n_total, fs,
-                       bs, bpf, bcs, rel, csizes, nframes);
+hipError_t lzh_launch_frame_sizes(const LzhInput& I, int codec, int params, const uint32_t* bcs, uint32_t* rel,
+                                  uint32_t* csizes, hipStream_t s) {
+    if (!I.nframes) return hipSuccess;
+    hipLaunchKernelGGL(lzh_frame_size_kernel, dim3((I.nframes + 255) / 256), dim3(256), 0, s, codec, params, I.n_total,
+                       I.frame_size, I.chunk_size, I.bpf, bcs, rel, csizes, I.nframes);
     return hipGetLastError();
 }
-hipError_t lzh_launch_frame_pack(int codec, int params, const uint8_t* in, uint64_t n_total, uint64_t in_readable,
-                                 uint64_t fs, uint64_t bs, uint32_t bpf, const uint8_t* stage, uint64_t stride,
-                                 const uint32_t* bcs, const uint32_t* rel, const uint32_t* csizes,
-                                 const uint64_t* offsets, uint8_t* packed, uint32_t nblocks, uint32_t nframes,
-                                 hipStream_t s) {
-    if (!nframes) return hipSuccess;
-    hipLaunchKernelGGL(lzh_frame_pack_kernel, dim3(nblocks + nframes), dim3(256), 0, s, codec, params, in, n_total,
-                       in_readable, fs, bs, bpf, stage, stride, bcs, rel, csizes, offsets, packed, nblocks);
+hipError_t lzh_launch_frame_pack(const LzhInput& I, int codec, int params, const LzhFrameSlots& F, const uint32_t* csizes,
+                                 const uint64_t* offsets, uint8_t* packed, hipStream_t s) {
+    if (!I.nframes) return hipSuccess;
+    hipLaunchKernelGGL(lzh_frame_pack_kernel, dim3(I.nchunks + I.nframes), dim3(256), 0, s, codec, params, I.in, I.n_total,
+                       I.in_readable, I.frame_size, I.chunk_size, I.bpf, F.blocks.stage, F.blocks.stride, F.bcs, F.rel, csizes,
+                       offsets, packed, I.nchunks);
     return hipGetLastError();
 }
 hipError_t lzh_launch_frame_parse(int codec, const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,

@@ -4,12 +4,37 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-hipError_t lzh_launch_lz4_compress_v2(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                      int acc, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                      hipStream_t s);
-hipError_t lzh_launch_snappy_compress_v2(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                         uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                         hipStream_t s);
+// What every uniform compress launcher below is handed (include/lzbench_hip.h 3; api.cpp's uniform_call forms them
+// once per call, the layouts of temp_layout.h hand out the slots).  The input: nchunks chunks, chunk i = the bytes from
+// i * chunk_size of `in` (n_total bytes, in_readable may be read).  Framed layouts (LZ4 frame, nvcomp container): the
+// chunks are the blocks -- block i is block i mod bpf of frame i / bpf, nframes frames of frame_size bytes cut into
+// blocks of chunk_size.  bpf <= 1: plain chunks (frame_size unused, nframes = nchunks).
+struct LzhInput {
+    const uint8_t* in;
+    uint64_t n_total, in_readable, chunk_size;
+    uint32_t nchunks;
+    uint64_t frame_size;
+    uint32_t bpf, nframes;
+};
+// Uniform slots, each sized for the largest chunk (ragged: max_bytes), slot i for chunk i: staging slots of `stride`
+// bytes; at recs, rec_stride apart, the LZ4 / snappy record slots or the zstd kernels' per-frame scratch areas (null /
+// 0: the call has none); hdr: the per-chunk record counts (null where there are no records).
+struct LzhSlots {
+    uint8_t* stage;
+    uint64_t stride;
+    uint8_t* recs;
+    uint64_t rec_stride;
+    uint32_t* hdr;
+};
+// The slots of a framed layout: the blocks' slots (linked frames: the per-frame table snapshots, 16 KiB each, at
+// blocks.recs), the block sizes and the block offsets inside their frame.
+struct LzhFrameSlots {
+    LzhSlots blocks;
+    uint32_t *bcs, *rel;
+};
+
+hipError_t lzh_launch_lz4_compress_v2(const LzhInput& I, int acc, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_snappy_compress_v2(const LzhInput& I, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
 // desc: 32-byte block descriptors (frame_hip.hip) instead of chunk geometry + offsets / csizes
 hipError_t lzh_launch_decompress(int codec, const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                  const uint32_t* csizes, uint64_t n_total, uint64_t chunk_size, uint8_t* out,
@@ -29,27 +54,22 @@ hipError_t lzh_launch_snappy_split_decompress(const uint8_t* packed, uint64_t pa
                                               int32_t* status, uint32_t nchunks, uint8_t* temp, hipStream_t s);
 // smallest chunk the zstd split decoder takes (below it: the one-wave decoder, no temp)
 constexpr uint64_t lzh_zstd_split_min = 16384;
-hipError_t lzh_launch_scan(const uint32_t* csizes, uint64_t nchunks, uint64_t* offsets, uint64_t* total,
-                           hipStream_t s);
-hipError_t lzh_launch_pack(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                           const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
-                           uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s);
+hipError_t lzh_launch_scan(const uint32_t* csizes, uint64_t nchunks, uint64_t* offsets, uint64_t* total, hipStream_t s);
+hipError_t lzh_launch_pack(const LzhInput& I, const LzhSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                           uint8_t* packed, uint64_t packed_cap, hipStream_t s);
 hipError_t lzh_launch_memcpy(const void* src, void* dst, uint64_t n, hipStream_t s);
-hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                    int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                    uint8_t* scratch, hipStream_t s);
+// scratch areas at S.recs, lzh_zstd_scratch_stride(chunk_size, level) apart (S.rec_stride is the layout's bound on it)
+hipError_t lzh_launch_zstd_compress(const LzhInput& I, int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s);
 size_t lzh_zstd_scratch_stride(size_t chunk_size, int level);
 int lzh_zstd_level_ok(int level, size_t chunk_size);
 // dynamic LDS of the zstd match kernels for frames of up to chunk_size bytes (0: the hash table lives in scratch)
 uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size);
-// zstd level 3, the double-fast strategy (zstdc_dfast_hip.hip; LZH_CODEC_ZSTD_DFAST): staging slots as for
-// lzh_launch_zstd_compress, per-frame scratch areas of lzh_zstd_dfast_scratch_stride(chunk_size) -- the fast levels'
-// areas below the table, then the long and the short table, each the largest of any chunk size up to chunk_size.
-// One match / entropy pair per block index, every launch on s: no side stream, so a captured call has no parallel
-// branches.
-hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                          uint8_t* scratch, hipStream_t s);
+// zstd level 3, the double-fast strategy (zstdc_dfast_hip.hip; LZH_CODEC_ZSTD_DFAST): scratch areas at S.recs,
+// lzh_zstd_dfast_scratch_stride(chunk_size) apart -- the fast levels' areas below the table, then the long and the
+// short table, each the largest of any chunk size up to chunk_size.  One match / entropy pair per block index, every
+// launch on s: no side stream, so a captured call has no parallel branches.
+hipError_t lzh_launch_zstd_dfast_compress(const LzhInput& I, int level, const LzhSlots& S, uint32_t* csizes,
+                                          hipStream_t s);
 size_t lzh_zstd_dfast_scratch_stride(size_t chunk_size);
 // What every ragged compress launcher below is handed (include/lzbench_hip.h 3b .. 3h; api.cpp's ragged_compress
 // forms them, the layouts of temp_layout.h hand out the slots).
@@ -60,16 +80,6 @@ struct LzhBatch {
     const uint64_t* bytes;
     uint64_t max_bytes;
     uint32_t nchunks;
-};
-// Uniform slots, each sized for max_bytes, slot i for chunk i: staging slots of `stride` bytes; at recs, rec_stride
-// apart, the LZ4 / snappy record slots or the zstd kernels' per-frame scratch areas (null / 0: the call has none);
-// hdr: the per-chunk record counts (null where there are no records).
-struct LzhSlots {
-    uint8_t* stage;
-    uint64_t stride;
-    uint8_t* recs;
-    uint64_t rec_stride;
-    uint32_t* hdr;
 };
 
 // ragged zstd batches (zstd_ragged_hip.hip, zstd_ragged_decode_hip.hip, zstd_ragged_split_hip.hip;
@@ -129,21 +139,13 @@ LzhZstdHooks lzh_zstd_hooks(uint32_t nchunks);
 hipError_t lzh_launch_zstd_seq(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                uint64_t slot_bytes, uint32_t nchunks, int32_t* status, uint8_t* zt, const int32_t* zst,
                                void* zfr, hipStream_t s);
-// frame_size / bpf: framed layouts (LZ4 frame, nvcomp container) -- block i is block i mod bpf of
-// frame i / bpf (frames of frame_size bytes cut into blocks of chunk_size); bpf <= 1: plain chunks
-hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,
-                                  uint32_t bpf, int acc, uint8_t* stage, uint64_t stride, uint32_t* bcs, uint32_t* snap,
-                                  uint32_t nframes, hipStream_t s);
-// recs / rec_stride / hdr (here and in the snappy launcher below): the record slots and the per-chunk record counts
-// where the caller's temp layout puts them (ChunkTemp / FrameTemp, temp_layout.h)
-hipError_t lzh_launch_lz4_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
-                                uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                uint64_t rec_stride, uint32_t* hdr, int stage_mask, hipStream_t s,
-                                uint64_t frame_size = 0, uint32_t bpf = 1);
+// linked LZ4 frames, one wave per frame (I: the blocks of a framed layout; the block sizes go to F.bcs)
+hipError_t lzh_launch_lz4f_linked(const LzhInput& I, int acc, const LzhFrameSlots& F, hipStream_t s);
+// parse kernel, emit kernel: stage_mask bit 0 = parse, bit 1 = emit (framed layouts: csizes = the block sizes)
+hipError_t lzh_launch_lz4_split(const LzhInput& I, int acc, const LzhSlots& S, uint32_t* csizes, int stage_mask,
+                                hipStream_t s);
 size_t lzh_lz4_rec_stride(uint64_t chunk_size);
-hipError_t lzh_launch_snappy_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                   uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                   uint64_t rec_stride, uint32_t* hdr, int stage_mask, hipStream_t s);
+hipError_t lzh_launch_snappy_split(const LzhInput& I, const LzhSlots& S, uint32_t* csizes, int stage_mask, hipStream_t s);
 size_t lzh_snappy_rec_stride(uint64_t chunk_size);
 uint32_t lzh_snappy_frags(uint64_t chunk_size);
 // the emit kernel of a snappy launcher by waves per block: k1 for chunks of one fragment, else the kernel with
@@ -293,13 +295,11 @@ long lzh_zstd_dfast_dict_host_parse(int level, const uint8_t* dict, uint64_t dic
                                     uint32_t* seqs, uint64_t cap, uint64_t* events);
 
 // framed LZ4 layouts (frame_hip.hip); codec 4 = LZ4 frame, 5 = nvcomp LZ4 container
-hipError_t lzh_launch_frame_sizes(int codec, int params, uint64_t n_total, uint64_t fs, uint64_t bs, uint32_t bpf,
-                                  const uint32_t* bcs, uint32_t* rel, uint32_t* csizes, uint32_t nframes, hipStream_t s);
-hipError_t lzh_launch_frame_pack(int codec, int params, const uint8_t* in, uint64_t n_total, uint64_t in_readable,
-                                 uint64_t fs, uint64_t bs, uint32_t bpf, const uint8_t* stage, uint64_t stride,
-                                 const uint32_t* bcs, const uint32_t* rel, const uint32_t* csizes,
-                                 const uint64_t* offsets, uint8_t* packed, uint32_t nblocks, uint32_t nframes,
-                                 hipStream_t s);
+// (I: the blocks of the framed layout; params: the call's level; csizes: the frame sizes)
+hipError_t lzh_launch_frame_sizes(const LzhInput& I, int codec, int params, const uint32_t* bcs, uint32_t* rel,
+                                  uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_frame_pack(const LzhInput& I, int codec, int params, const LzhFrameSlots& F, const uint32_t* csizes,
+                                 const uint64_t* offsets, uint8_t* packed, hipStream_t s);
 hipError_t lzh_launch_frame_parse(int codec, const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
                                   const uint32_t* csizes, uint64_t n_total, uint64_t fs, uint32_t maxbpf, void* desc,
                                   int32_t* fstat, uint32_t nframes, hipStream_t s);

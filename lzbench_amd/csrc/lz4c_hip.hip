@@ -189,41 +189,39 @@ lzh_lz4f_linked_kernel(const uint8_t* in, uint64_t n_total, uint64_t in_readable
 #include "launch.h"
 size_t lzh_lz4_rec_stride(uint64_t chunk_size) { return ((chunk_size / 4 + 4) * 8 + 255) / 256 * 256; }
 
-hipError_t lzh_launch_lz4_compress_v2(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                      int acc, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                      hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_lz4_compress_v2_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable,
-                       chunk_size, acc, stage, stride, csizes, 0u, (unsigned long long*)nullptr);
+hipError_t lzh_launch_lz4_compress_v2(const LzhInput& I, int acc, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_lz4_compress_v2_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                       I.chunk_size, acc, S.stage, S.stride, csizes, 0u, (unsigned long long*)nullptr);
     return hipGetLastError();
 }
 
-// parse kernel + emit kernel (records in `recs`: nchunks x rs bytes; 8 bytes per chunk at `hdr`);
+// parse kernel + emit kernel (records in S.recs: nchunks x S.rec_stride bytes; 8 bytes per chunk at S.hdr);
 // stage_mask bit 0 = parse, bit 1 = emit (profiling runs one of them)
-hipError_t lzh_launch_lz4_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size, int acc,
-                                uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                uint64_t rs, uint32_t* hdr, int stage_mask, hipStream_t s, uint64_t frame_size,
-                                uint32_t bpf) {
-    if (nchunks == 0) return hipSuccess;
-    if (bpf <= 1) { bpf = 1; frame_size = chunk_size; }
+hipError_t lzh_launch_lz4_split(const LzhInput& I, int acc, const LzhSlots& S, uint32_t* csizes, int stage_mask,
+                                hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    const bool framed = I.bpf > 1;
+    const uint64_t frame_size = framed ? I.frame_size : I.chunk_size;
+    const uint32_t bpf = framed ? I.bpf : 1;
     if (stage_mask & 1)
-        hipLaunchKernelGGL(lzh_lz4_parse_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable, chunk_size,
-                           acc, recs, rs, hdr, frame_size, bpf);
+        hipLaunchKernelGGL(lzh_lz4_parse_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                           I.chunk_size, acc, S.recs, S.rec_stride, S.hdr, frame_size, bpf);
     if (stage_mask & 2)
-        hipLaunchKernelGGL(lzh_lz4_emit_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable, chunk_size,
-                           (const uint8_t*)recs, rs, (const uint32_t*)hdr, stage, stride, csizes, frame_size, bpf);
+        hipLaunchKernelGGL(lzh_lz4_emit_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                           I.chunk_size, (const uint8_t*)S.recs, S.rec_stride, (const uint32_t*)S.hdr, S.stage, S.stride,
+                           csizes, frame_size, bpf);
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_lz4f_linked(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t fs, uint64_t bs,
-                                  uint32_t bpf, int acc, uint8_t* stage, uint64_t stride, uint32_t* bcs, uint32_t* snap,
-                                  uint32_t nframes, hipStream_t s) {
-    if (nframes == 0) return hipSuccess;
+hipError_t lzh_launch_lz4f_linked(const LzhInput& I, int acc, const LzhFrameSlots& F, hipStream_t s) {
+    if (I.nframes == 0) return hipSuccess;
 #ifdef LZH_NO_LINKED_KERNEL
     return hipErrorNotSupported;
 #else
-    hipLaunchKernelGGL(lzh_lz4f_linked_kernel, dim3(nframes), dim3(64), 0, s, in, n_total, in_readable, fs, bs, bpf, acc,
-                       stage, stride, bcs, snap);
+    hipLaunchKernelGGL(lzh_lz4f_linked_kernel, dim3(I.nframes), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                       I.frame_size, I.chunk_size, I.bpf, acc, F.blocks.stage, F.blocks.stride, F.bcs,
+                       (uint32_t*)F.blocks.recs);
     return hipGetLastError();
 #endif
 }

@@ -56,12 +56,11 @@ hipError_t lzh_launch_scan(const uint32_t* csizes, uint64_t nchunks, uint64_t* o
     hipLaunchKernelGGL(lzh_scan_kernel, dim3(1), dim3(1024), 0, s, csizes, nchunks, offsets, total);
     return hipGetLastError();
 }
-hipError_t lzh_launch_pack(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                           const uint8_t* stage, uint64_t stride, const uint32_t* csizes, const uint64_t* offsets,
-                           uint8_t* packed, uint64_t packed_cap, uint32_t nchunks, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_pack_kernel, dim3(nchunks), dim3(256), 0, s, in, n_total, in_readable, chunk_size,
-                       stage, stride, csizes, offsets, packed, packed_cap);
+hipError_t lzh_launch_pack(const LzhInput& I, const LzhSlots& S, const uint32_t* csizes, const uint64_t* offsets,
+                           uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_pack_kernel, dim3(I.nchunks), dim3(256), 0, s, I.in, I.n_total, I.in_readable, I.chunk_size,
+                       S.stage, S.stride, csizes, offsets, packed, packed_cap);
     return hipGetLastError();
 }
 hipError_t lzh_launch_memcpy(const void* src, void* dst, uint64_t n, hipStream_t s) {

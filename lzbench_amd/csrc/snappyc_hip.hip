@@ -88,31 +88,27 @@ size_t lzh_snappy_rec_stride(uint64_t chunk_size) {
     return ((chunk_size / 4 + 8) * 8 + 255) / 256 * 256;
 }
 
-// parse kernel + emit kernel (records in `recs`: nchunks x rs bytes; a u32 count per fragment at `hdr`);
+// parse kernel + emit kernel (records in S.recs: nchunks x S.rec_stride bytes; a u32 count per fragment at S.hdr);
 // stage_mask bit 0 = parse, bit 1 = emit
-hipError_t lzh_launch_snappy_split(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                   uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks, uint8_t* recs,
-                                   uint64_t rs, uint32_t* hdr, int stage_mask, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    const uint32_t frags = lzh_snappy_frags(chunk_size);
+hipError_t lzh_launch_snappy_split(const LzhInput& I, const LzhSlots& S, uint32_t* csizes, int stage_mask, hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    const uint32_t frags = lzh_snappy_frags(I.chunk_size);
     if (stage_mask & 1)
-        hipLaunchKernelGGL(lzh_snappy_parse_kernel, dim3(nchunks * frags), dim3(64), 0, s, in, n_total, in_readable,
-                           chunk_size, recs, rs, hdr, frags);
+        hipLaunchKernelGGL(lzh_snappy_parse_kernel, dim3(I.nchunks * frags), dim3(64), 0, s, I.in, I.n_total,
+                           I.in_readable, I.chunk_size, S.recs, S.rec_stride, S.hdr, frags);
     if (stage_mask & 2) {
         if (frags > (uint32_t)sne::kMaxFrags) return hipErrorInvalidValue;
         lzh_launch_snappy_emit(lzh_snappy_emit_kernel, lzh_snappy_emit_frag_kernel<2>, lzh_snappy_emit_frag_kernel<4>,
-                               lzh_snappy_emit_frag_kernel<8>, frags, nchunks, s, in, n_total, in_readable, chunk_size,
-                               recs, rs, hdr, stage, stride, csizes, frags);
+                               lzh_snappy_emit_frag_kernel<8>, frags, I.nchunks, s, I.in, I.n_total, I.in_readable,
+                               I.chunk_size, S.recs, S.rec_stride, S.hdr, S.stage, S.stride, csizes, frags);
     }
     return hipGetLastError();
 }
 
-hipError_t lzh_launch_snappy_compress_v2(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                         uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                         hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lzh_snappy_compress_v2_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable,
-                       chunk_size, stage, stride, csizes, 0u, (unsigned long long*)nullptr);
+hipError_t lzh_launch_snappy_compress_v2(const LzhInput& I, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(lzh_snappy_compress_v2_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                       I.chunk_size, S.stage, S.stride, csizes, 0u, (unsigned long long*)nullptr);
     return hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ static inline size_t zstd_dfast_scratch_stride(size_t chunk) { return lzh_zstd_d
 struct ChunkTemp {
     bool split;
     size_t stride, rec_stride, stage, recs, hdr, total;
-    LzhSlots slots(uint8_t* base) const {   // (the ragged launchers' bundle; record counts only where there are records)
+    LzhSlots slots(uint8_t* base) const {   // (the launchers' bundle; record counts only where there are records)
         return {base + stage, stride, base + recs, rec_stride, split ? (uint32_t*)(base + hdr) : nullptr};
     }
 };
@@ -143,7 +143,13 @@ static inline FrameGeo frame_geo(size_t B, size_t n, size_t F) {
     return g;
 }
 
-struct FrameTemp { size_t stride, rec_stride, stage, recs, hdr, bcs, rel, total; };
+struct FrameTemp {
+    size_t stride, rec_stride, stage, recs, hdr, bcs, rel, total;
+    LzhFrameSlots slots(uint8_t* base) const {
+        return {{base + stage, stride, base + recs, rec_stride, (uint32_t*)(base + hdr)}, (uint32_t*)(base + bcs),
+                (uint32_t*)(base + rel)};
+    }
+};
 static inline FrameTemp frame_temp(const FrameGeo& g) {
     FrameTemp t;
     TempCursor c;

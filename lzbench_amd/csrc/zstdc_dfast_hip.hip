@@ -67,21 +67,23 @@ size_t lzh_zstd_dfast_scratch_stride(size_t chunk_size) {
     return (size_t)((Lo.tab_off + (4ull << hmax) + (4ull << cmax) + 255) & ~255ull);
 }
 
-hipError_t lzh_launch_zstd_dfast_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                          int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                          uint8_t* scratch, hipStream_t s) {
-    if (nchunks == 0) return hipSuccess;
-    const zdf::DParams PF = zdf::params_for(level, chunk_size);
+hipError_t lzh_launch_zstd_dfast_compress(const LzhInput& I, int level, const LzhSlots& S, uint32_t* csizes,
+                                          hipStream_t s) {
+    if (I.nchunks == 0) return hipSuccess;
+    const zdf::DParams PF = zdf::params_for(level, I.chunk_size);
     if (!PF.ok) return hipErrorInvalidValue;
-    const uint64_t fstride = lzh_zstd_dfast_scratch_stride(chunk_size);
+    // (the stride computed here, as in lzh_launch_zstd_compress; this codec's layout has the one level, so
+    // S.rec_stride is the same number)
+    const uint64_t fstride = lzh_zstd_dfast_scratch_stride(I.chunk_size);
     const Layout Lo = layout_for(PF.bsize, 16);
-    const uint32_t nblocks = (uint32_t)((std::min<uint64_t>(chunk_size, std::max<uint64_t>(n_total, 1)) + PF.bsize - 1) / PF.bsize);
+    const uint32_t nblocks =
+        (uint32_t)((std::min<uint64_t>(I.chunk_size, std::max<uint64_t>(I.n_total, 1)) + PF.bsize - 1) / PF.bsize);
     for (uint32_t k = 0; k < std::max(nblocks, 1u); k++) {
-        hipLaunchKernelGGL(lzh_zstd_dfast_match_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable, chunk_size,
-                           level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off);
-        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_kernel, dim3(nchunks), dim3(64), 0, s, in, n_total, in_readable,
-                           chunk_size, level, (int)k, scratch, fstride, Lo.seq_off, Lo.lit_off, Lo.att_off, Lo.tmp_off,
-                           stage, stride, csizes);
+        hipLaunchKernelGGL(lzh_zstd_dfast_match_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total, I.in_readable,
+                           I.chunk_size, level, (int)k, S.recs, fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off);
+        hipLaunchKernelGGL(lzh_zstd_dfast_entropy_kernel, dim3(I.nchunks), dim3(64), 0, s, I.in, I.n_total,
+                           I.in_readable, I.chunk_size, level, (int)k, S.recs, fstride, Lo.seq_off, Lo.lit_off,
+                           Lo.att_off, Lo.tmp_off, S.stage, S.stride, csizes);
     }
     return hipGetLastError();
 }

@@ -91,26 +91,28 @@ uint32_t lzh_zstd_lds_table(int level, uint64_t chunk_size) {
            : chunk_size <= 131072u ? ((t17 + 15u) & ~15u) : (ebytes << PF.hlog);
 }
 
-hipError_t lzh_launch_zstd_compress(const uint8_t* in, uint64_t n_total, uint64_t in_readable, uint64_t chunk_size,
-                                    int level, uint8_t* stage, uint64_t stride, uint32_t* csizes, uint32_t nchunks,
-                                    uint8_t* scratch, hipStream_t s) {
+hipError_t lzh_launch_zstd_compress(const LzhInput& I, int level, const LzhSlots& S, uint32_t* csizes, hipStream_t s) {
+    const uint32_t nchunks = I.nchunks;
     if (nchunks == 0) return hipSuccess;
-    const ZParams P = params_for(level, std::min<uint64_t>(chunk_size, n_total ? n_total : 0));
+    const ZParams P = params_for(level, std::min<uint64_t>(I.chunk_size, I.n_total ? I.n_total : 0));
     if (!P.ok) return hipErrorInvalidValue;
-    const ZParams PF = params_for(level, chunk_size);
-    const size_t fstride = lzh_zstd_scratch_stride(chunk_size, level);
+    const ZParams PF = params_for(level, I.chunk_size);
+    // the scratch areas are this level's stride apart: S.rec_stride, the layout's largest stride of any level, is here
+    // (and nowhere else) an upper bound and not the stride in use -- of the scratch, only S.recs is read
+    const size_t fstride = lzh_zstd_scratch_stride(I.chunk_size, level);
     const Layout Lo = layout_for(PF.bsize, 16);   // offsets below tab_off do not depend on hlog
-    const uint32_t nblocks = (uint32_t)((std::min<uint64_t>(chunk_size, std::max<uint64_t>(n_total, 1)) + PF.bsize - 1) / PF.bsize);
-    const uint32_t lds_tab = lzh_zstd_lds_table(level, chunk_size);
+    const uint32_t nblocks =
+        (uint32_t)((std::min<uint64_t>(I.chunk_size, std::max<uint64_t>(I.n_total, 1)) + PF.bsize - 1) / PF.bsize);
+    const uint32_t lds_tab = lzh_zstd_lds_table(level, I.chunk_size);
     auto match = [&](hipStream_t st, uint32_t k, uint32_t f0, uint32_t nf) {
-        hipLaunchKernelGGL(lzh_zstd_match_kernel, dim3(nf), dim3(64), lds_tab, st, in, n_total, in_readable,
-                           chunk_size, level, (int)k, scratch, (uint64_t)fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off,
+        hipLaunchKernelGGL(lzh_zstd_match_kernel, dim3(nf), dim3(64), lds_tab, st, I.in, I.n_total, I.in_readable,
+                           I.chunk_size, level, (int)k, S.recs, (uint64_t)fstride, Lo.seq_off, Lo.lit_off, Lo.tab_off,
                            lds_tab, f0);
     };
     auto entropy = [&](hipStream_t st, uint32_t k, uint32_t f0, uint32_t nf) {
-        hipLaunchKernelGGL(lzh_zstd_entropy_kernel, dim3(nf), dim3(64), 0, st, in, n_total, in_readable,
-                           chunk_size, level, (int)k, scratch, (uint64_t)fstride, Lo.seq_off, Lo.lit_off, Lo.att_off,
-                           Lo.tmp_off, stage, stride, csizes, f0);
+        hipLaunchKernelGGL(lzh_zstd_entropy_kernel, dim3(nf), dim3(64), 0, st, I.in, I.n_total, I.in_readable,
+                           I.chunk_size, level, (int)k, S.recs, (uint64_t)fstride, Lo.seq_off, Lo.lit_off, Lo.att_off,
+                           Lo.tmp_off, S.stage, S.stride, csizes, f0);
     };
     // Single-block frames: a frame's entropy stage needs only its own match stage, so the frames split in
     // two.  The first half runs match + entropy on the caller stream's high-priority side stream (its waves go

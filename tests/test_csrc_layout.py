@@ -184,6 +184,27 @@ def test_api_packs_and_tests_its_pointers_in_one_place():
     assert len(re.findall(r"d_in_ptrs\s*&&", code)) == 1
 
 
+# The uniform compress calls: the input struct and the slots of the call's layout from api.cpp's uniform_call to the
+# launchers (launch.h LzhInput, LzhSlots, LzhFrameSlots).
+def test_launch_h_names_the_input_in_the_input_struct_alone():
+    code = _code(_sources()["launch.h"])
+    assert re.search(r"struct LzhInput \{\s*const uint8_t\* in;\s*uint64_t n_total, in_readable, chunk_size;", code)
+    assert len(re.findall(r"\bin_readable\b", code)) == 1
+    assert len(re.findall(r"\bstruct \w*Slots \{", code)) == 3   # (LzhSlots, LzhFrameSlots, LzhCompactSlots)
+
+
+def test_api_has_one_uniform_scan_and_pack_and_one_range_check():
+    code = _code(_sources()["api.cpp"])
+    for launcher in ("lzh_launch_pack(", "lzh_launch_frame_pack("):
+        assert code.count(launcher) == 1, launcher
+    assert code.count("0x7fff0000u") == 1
+    # the layouts hand out the slots: no offset arithmetic in the compress calls
+    uniform = code[code.index("static bool fits_u32("):code.index("int lzh_decompress_async(")]
+    assert "lzh_compress_finish_async(" in uniform and not re.search(r"\bbase \+", uniform)
+    for layout in ("chunk_temp(", "frame_temp(", "frame_geo("):
+        assert uniform.count(layout) == 1, layout
+
+
 @pytest.mark.parametrize("header", COMPRESS_HEADERS + (DICT_ENV,))
 def test_compress_header_compiles_when_included_first(header, tmp_path):
     r = _syntax_check(tmp_path, '#include "%s"\n' % header)
