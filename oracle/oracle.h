@@ -76,6 +76,53 @@ int64_t oracle_snappy_uncompress(const uint8_t* src, size_t csize, uint8_t* dst,
  * oracle_zstd_bound(n) + 64 bytes.  Returns the frame size, or -1 for an unsupported level. */
 int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int level);
 size_t oracle_zstd_bound(size_t n);
+/* The same compressor, counting the decisions of its entropy stage into c[ORACLE_ZSE_N] (added to what c holds; the
+ * bytes written are oracle_zstd_compress's: one body; c == NULL counts nothing).  tests/zstd_entropy_census.py names
+ * and documents the events, in this order.  The FSE events (NORM_FAST .. NC_FLUSH_MID_RUN) exist once per call site:
+ * index + ORACLE_ZSE_FSE_STRIDE * site, site 0 = the sequence tables, 1 = the Huffman weights.  The per-table events
+ * (TYPE_RLE .. TLOG_9) exist three times: index + ORACLE_ZSE_TAB_STRIDE * table, table 0 = LL, 1 = OF, 2 = ML. */
+enum {
+    ORACLE_ZSE_LIT_GATE_LE63, ORACLE_ZSE_LIT_GATE_63, ORACLE_ZSE_LIT_GATE_64, ORACLE_ZSE_LIT_OFF,
+    ORACLE_ZSE_LIT_SAMPLED_RAW, ORACLE_ZSE_LIT_SAMPLED_PASSED, ORACLE_ZSE_LIT_SUSPECT_19, ORACLE_ZSE_LIT_SUSPECT_20,
+    ORACLE_ZSE_LIT_RLE, ORACLE_ZSE_LIT_FLAT_RAW, ORACLE_ZSE_LIT_REPEAT_INVALID, ORACLE_ZSE_LIT_REPEAT_SMALL_DIRECT,
+    ORACLE_ZSE_LIT_REPEAT_OLD_BY_ESTIMATE, ORACLE_ZSE_LIT_REPEAT_OLD_BY_H12, ORACLE_ZSE_LIT_REPEAT_NEW_TABLE,
+    ORACLE_ZSE_LIT_RAW_H12, ORACLE_ZSE_LIT_RAW_STREAMS_OLD, ORACLE_ZSE_LIT_RAW_STREAMS_NEW, ORACLE_ZSE_LIT_RAW_MINGAIN,
+    ORACLE_ZSE_LIT_HDR_3, ORACLE_ZSE_LIT_HDR_4, ORACLE_ZSE_LIT_HDR_5, ORACLE_ZSE_LIT_STREAMS_1, ORACLE_ZSE_LIT_STREAMS_4,
+    ORACLE_ZSE_LIT_STREAM_GT_65535,
+    ORACLE_ZSE_HUF_MAXNB_5, ORACLE_ZSE_HUF_MAXNB_6, ORACLE_ZSE_HUF_MAXNB_7, ORACLE_ZSE_HUF_MAXNB_8, ORACLE_ZSE_HUF_MAXNB_9,
+    ORACLE_ZSE_HUF_MAXNB_10, ORACLE_ZSE_HUF_MAXNB_11, ORACLE_ZSE_HUF_MAXNB_BY_MAX11, ORACLE_ZSE_HUF_MAXNB_BY_SRCSIZE,
+    ORACLE_ZSE_HUF_MAXNB_BY_MINBITS, ORACLE_ZSE_HUF_MAXNB_BY_FLOOR5,
+    ORACLE_ZSE_HUF_LIMIT_NOT_NEEDED, ORACLE_ZSE_HUF_LIMIT_FIRED, ORACLE_ZSE_HUF_LIMIT_REPAY_DEC_GT1,
+    ORACLE_ZSE_HUF_LIMIT_REPAY_NO_SYMBOL, ORACLE_ZSE_HUF_LIMIT_OVERPAID, ORACLE_ZSE_HUF_LIMIT_OVERPAID_RANK1_EMPTY,
+    ORACLE_ZSE_HUF_SORT_BUCKET_GE165, ORACLE_ZSE_HUF_SORT_PARTITIONED,
+    ORACLE_ZSE_HUF_W_WN_LE1, ORACLE_ZSE_HUF_W_RLE, ORACLE_ZSE_HUF_W_ALL_DISTINCT, ORACLE_ZSE_HUF_W_FSE,
+    ORACLE_ZSE_HUF_W_FSE_TOO_LARGE, ORACLE_ZSE_HUF_W_ODD_COUNT,
+    ORACLE_ZSE_HUF_TABLE_DIRECT, ORACLE_ZSE_HUF_TABLE_FSE, ORACLE_ZSE_HUF_TABLE_REFUSED,
+    ORACLE_ZSE_M2_TODIST_0, ORACLE_ZSE_M2_SECOND_PASS, ORACLE_ZSE_M2_ALL_LOW, ORACLE_ZSE_M2_TOTAL_0, ORACLE_ZSE_M2_SPREAD,
+    ORACLE_ZSE_SEQ_NS_MOD64_0, ORACLE_ZSE_SEQ_NS_MOD64_1, ORACLE_ZSE_SEQ_NS_MOD64_2, ORACLE_ZSE_SEQ_NS_MOD64_3,
+    ORACLE_ZSE_SEQ_NS_MOD64_4, ORACLE_ZSE_SEQ_NS_MOD64_5,
+    ORACLE_ZSE_SEQ_NS_1, ORACLE_ZSE_SEQ_NS_63, ORACLE_ZSE_SEQ_NS_64, ORACLE_ZSE_SEQ_NS_65, ORACLE_ZSE_SEQ_NS_128,
+    ORACLE_ZSE_SEQ_NS_129,
+    ORACLE_ZSE_SEQ_BITS_GE32, ORACLE_ZSE_SEQ_BITS_GE57, ORACLE_ZSE_SEQ_LL_GE65536, ORACLE_ZSE_SEQ_ML_GE65539,
+    ORACLE_ZSE_SEQ_OFCODE_GE17,
+    ORACLE_ZSE_BLOCK_LEN_LT7, ORACLE_ZSE_BLOCK_RAW_MINGAIN, ORACLE_ZSE_BLOCK_RAW_SEQUENCES_FAILED, ORACLE_ZSE_BLOCK_RLE,
+    ORACLE_ZSE_BLOCK_RLE_REFUSED_FIRST, ORACLE_ZSE_BLOCK_CMP_NEW_HUF_KEPT, ORACLE_ZSE_BLOCK_REPCODES_CONFIRMED,
+    ORACLE_ZSE_BLOCK_REPCODES_UNCONFIRMED,
+    ORACLE_ZSE_FSE0,                                       /* first FSE event of site 0 */
+    ORACLE_ZSE_NORM_FAST = ORACLE_ZSE_FSE0, ORACLE_ZSE_NORM_P_LT8_ROUNDED_UP, ORACLE_ZSE_NORM_LOW_MINUS1,
+    ORACLE_ZSE_NORM_LOW_PLUS1, ORACLE_ZSE_NORM_M2,
+    ORACLE_ZSE_NC_ZERO_RUN_0, ORACLE_ZSE_NC_ZERO_RUN_1_2, ORACLE_ZSE_NC_ZERO_RUN_3UP, ORACLE_ZSE_NC_ZERO_RUN_24UP,
+    ORACLE_ZSE_NC_COUNT_GE_THRESHOLD, ORACLE_ZSE_NC_ENDS_EARLY, ORACLE_ZSE_NC_FLUSH_MID_RUN,
+    ORACLE_ZSE_FSE_STRIDE = ORACLE_ZSE_NC_FLUSH_MID_RUN + 1 - ORACLE_ZSE_FSE0,
+    ORACLE_ZSE_TAB0 = ORACLE_ZSE_FSE0 + 2 * ORACLE_ZSE_FSE_STRIDE,     /* first per-table event of LL */
+    ORACLE_ZSE_TYPE_RLE = ORACLE_ZSE_TAB0, ORACLE_ZSE_TYPE_RLE_AS_PREDEF, ORACLE_ZSE_TYPE_PREDEF_BY_COUNT,
+    ORACLE_ZSE_TYPE_PREDEF_BY_FLATNESS, ORACLE_ZSE_TYPE_FSE, ORACLE_ZSE_TYPE_DEFAULT_REFUSED,
+    ORACLE_ZSE_LAST_COUNT_TAKEN, ORACLE_ZSE_LAST_COUNT_NOT,
+    ORACLE_ZSE_TLOG_5, ORACLE_ZSE_TLOG_6, ORACLE_ZSE_TLOG_7, ORACLE_ZSE_TLOG_8, ORACLE_ZSE_TLOG_9,
+    ORACLE_ZSE_TAB_STRIDE = ORACLE_ZSE_TLOG_9 + 1 - ORACLE_ZSE_TAB0,
+    ORACLE_ZSE_N = ORACLE_ZSE_TAB0 + 3 * ORACLE_ZSE_TAB_STRIDE
+};
+int64_t oracle_zstd_compress_census(const uint8_t* src, size_t n, uint8_t* dst, int level, uint64_t* c);
 
 /* Framed LZ4 formats (frame_oracle.c).  LZ4 frame as LZ4F_compressFrame writes it with
  * independent blocks (lz4frame.c:373-1019); params: bits 0-2 blockSizeID (0 = default 64 KiB, 4..7),

@@ -37,6 +37,16 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 typedef int16_t s16;
 
+/* entropy-stage events (oracle.h ORACLE_ZSE_*; tests/zstd_entropy_census.py names them).  The counter array of the
+ * call in progress, per thread (the _mt chunk loops compress from several threads); NULL: nothing is counted.
+ * ev_site: the FSE call site whose events EVF counts (0 the sequence tables, 1 the Huffman weights). */
+static __thread u64* ev_c;
+static __thread int ev_site;
+#define EV(i) do { if (ev_c) ev_c[ORACLE_ZSE_##i]++; } while (0)
+#define EVK(i, k) do { if (ev_c) ev_c[ORACLE_ZSE_##i + (k)]++; } while (0)
+#define EVF(i) EVK(i, ORACLE_ZSE_FSE_STRIDE * ev_site)
+#define EVT(i, t) EVK(i, ORACLE_ZSE_TAB_STRIDE * (t))
+
 static u32 hb32(u32 v) { return 31u - (u32)__builtin_clz(v); }
 static u32 rd32(const u8* p) { u32 v; memcpy(&v, p, 4); return v; }
 static u64 rd64(const u8* p) { u64 v; memcpy(&v, p, 8); return v; }
@@ -176,24 +186,28 @@ static int fse_norm_m2(s16* norm, u32 tl, const u32* cnt, size_t total, u32 maxs
         norm[s] = NA;
     }
     u32 toDist = (1u << tl) - distributed;
-    if (toDist == 0) return 0;
+    if (toDist == 0) { EV(M2_TODIST_0); return 0; }
     if ((total / toDist) > lowOne) {
+        EV(M2_SECOND_PASS);
         lowOne = (u32)((total * 3) / (toDist * 2));
         for (u32 s = 0; s <= maxs; s++)
             if (norm[s] == NA && cnt[s] <= lowOne) { norm[s] = 1; distributed++; total -= cnt[s]; }
         toDist = (1u << tl) - distributed;
     }
     if (distributed == maxs + 1) {
+        EV(M2_ALL_LOW);
         u32 mv = 0, mc = 0;
         for (u32 s = 0; s <= maxs; s++) if (cnt[s] > mc) { mv = s; mc = cnt[s]; }
         norm[mv] += (s16)toDist;
         return 0;
     }
     if (total == 0) {
+        EV(M2_TOTAL_0);
         for (u32 s = 0; toDist > 0; s = (s + 1) % (maxs + 1))
             if (norm[s] > 0) { toDist--; norm[s]++; }
         return 0;
     }
+    EV(M2_SPREAD);
     {
         const u64 vlog = 62 - tl;
         const u64 mid = (1ull << (vlog - 1)) - 1;
@@ -227,17 +241,23 @@ static int fse_normalize(s16* norm, u32 tl, const u32* cnt, size_t total, u32 ma
     for (u32 s = 0; s <= maxs; s++) {
         if (cnt[s] == total) return 0;       /* rle: not reached (callers check) */
         if (cnt[s] == 0) { norm[s] = 0; continue; }
-        if (cnt[s] <= lowThreshold) { norm[s] = low; still--; continue; }
+        if (cnt[s] <= lowThreshold) {
+            if (useLow) EVF(NORM_LOW_MINUS1); else EVF(NORM_LOW_PLUS1);
+            norm[s] = low; still--; continue;
+        }
         s16 p = (s16)((cnt[s] * step) >> scale);
         if (p < 8) {
             const u64 rest = vstep * rtb[p];
-            p += (s16)((cnt[s] * step) - ((u64)p << scale) > rest);
+            const int up = (cnt[s] * step) - ((u64)p << scale) > rest;
+            if (up) EVF(NORM_P_LT8_ROUNDED_UP);
+            p += (s16)up;
         }
         if (p > largestP) { largestP = p; largest = s; }
         norm[s] = p;
         still -= p;
     }
-    if (-still >= (norm[largest] >> 1)) return fse_norm_m2(norm, tl, cnt, total, maxs, low);
+    if (-still >= (norm[largest] >> 1)) { EVF(NORM_M2); return fse_norm_m2(norm, tl, cnt, total, maxs, low); }
+    EVF(NORM_FAST);
     norm[largest] += (s16)still;
     return 0;
 }
@@ -259,6 +279,11 @@ static size_t fse_write_ncount(u8* out, const s16* norm, u32 maxs, u32 tl) {
             u32 start = sym;
             while (sym < alpha && !norm[sym]) sym++;
             if (sym == alpha) break;
+            /* sym - start: the zero-probability symbols after the one that set prev0 */
+            if (sym == start) EVF(NC_ZERO_RUN_0);
+            else if (sym < start + 3) EVF(NC_ZERO_RUN_1_2);
+            else EVF(NC_ZERO_RUN_3UP);
+            if (sym >= start + 24) EVF(NC_ZERO_RUN_24UP);
             while (sym >= start + 24) {
                 start += 24;
                 bits += 0xFFFFu << nb;
@@ -268,14 +293,14 @@ static size_t fse_write_ncount(u8* out, const s16* norm, u32 maxs, u32 tl) {
             while (sym >= start + 3) { start += 3; bits += 3u << nb; nb += 2; }
             bits += (sym - start) << nb;
             nb += 2;
-            if (nb > 16) { o[0] = (u8)bits; o[1] = (u8)(bits >> 8); o += 2; bits >>= 16; nb -= 16; }
+            if (nb > 16) { EVF(NC_FLUSH_MID_RUN); o[0] = (u8)bits; o[1] = (u8)(bits >> 8); o += 2; bits >>= 16; nb -= 16; }
         }
         {
             int c = norm[sym++];
             const int mx = (2 * threshold - 1) - remaining;
             remaining -= c < 0 ? -c : c;
             c++;
-            if (c >= threshold) c += mx;
+            if (c >= threshold) { EVF(NC_COUNT_GE_THRESHOLD); c += mx; }
             bits += (u32)c << nb;
             nb += nbBits;
             nb -= (c < mx);
@@ -284,6 +309,7 @@ static size_t fse_write_ncount(u8* out, const s16* norm, u32 maxs, u32 tl) {
         }
         if (nb > 16) { o[0] = (u8)bits; o[1] = (u8)(bits >> 8); o += 2; bits >>= 16; nb -= 16; }
     }
+    if (sym < alpha) EVF(NC_ENDS_EARLY);       /* remaining <= 1 (or only zeros left) before the alphabet's end */
     o[0] = (u8)bits; o[1] = (u8)(bits >> 8);
     o += (nb + 7) / 8;
     return (size_t)(o - out);
@@ -377,6 +403,7 @@ static int huf_partition(hnode* a, int lo, int hi) {
 }
 static void huf_qsort(hnode* a, int lo, int hi) {
     if (hi - lo < 8) { huf_isort(a, lo, hi); return; }
+    EV(HUF_SORT_PARTITIONED);
     while (lo < hi) {
         const int p = huf_partition(a, lo, hi);
         if (p - lo < hi - p) { huf_qsort(a, lo, p - 1); lo = p + 1; }
@@ -397,14 +424,15 @@ static void huf_sort(hnode* node, const u32* cnt, u32 maxs) {
     }
     for (u32 b = 165; b < 191; b++) {
         const u32 sz = (u32)cur[b] - base[b];
-        if (sz > 1) huf_qsort(node + base[b], 0, (int)sz - 1);
+        if (sz > 1) { EV(HUF_SORT_BUCKET_GE165); huf_qsort(node + base[b], 0, (int)sz - 1); }
     }
 }
 
 /* HUF_setMaxHeight (huf_compress.c:308-428) */
 static u32 huf_limit(hnode* node, u32 last, u32 maxNb) {
     const u32 largest = node[last].nbBits;
-    if (largest <= maxNb) return largest;
+    if (largest <= maxNb) { EV(HUF_LIMIT_NOT_NEEDED); return largest; }
+    EV(HUF_LIMIT_FIRED);
     int cost = 0;
     const u32 baseCost = 1u << (largest - maxNb);
     int n = (int)last;
@@ -433,7 +461,9 @@ static u32 huf_limit(hnode* node, u32 last, u32 maxNb) {
                 if (lo == NONE) break;
                 if (node[hi].count <= 2 * node[lo].count) break;
             }
+            if (dec <= 12 && rankLast[dec] == NONE) EV(HUF_LIMIT_REPAY_NO_SYMBOL);
             while (dec <= 12 && rankLast[dec] == NONE) dec++;
+            if (dec > 1) EV(HUF_LIMIT_REPAY_DEC_GT1);
             cost -= 1 << (dec - 1);
             node[rankLast[dec]].nbBits++;
             if (rankLast[dec - 1] == NONE) rankLast[dec - 1] = rankLast[dec];
@@ -443,8 +473,10 @@ static u32 huf_limit(hnode* node, u32 last, u32 maxNb) {
                 if (node[rankLast[dec]].nbBits != maxNb - dec) rankLast[dec] = NONE;
             }
         }
+        if (cost < 0) EV(HUF_LIMIT_OVERPAID);
         while (cost < 0) {
             if (rankLast[1] == NONE) {
+                EV(HUF_LIMIT_OVERPAID_RANK1_EMPTY);
                 while (node[n].nbBits == maxNb) n--;
                 node[n + 1].nbBits--;
                 rankLast[1] = (u32)(n + 1);
@@ -514,15 +546,19 @@ static int huf_valid(const huf_ct* ct, const u32* cnt, u32 maxs) {
 /* FSE compression of the Huffman weights (HUF_compressWeights, huf_compress.c:92-129 +
  * FSE_compress_usingCTable_generic, fse_compress.c:593-650); 0 = not compressible, 1 = rle */
 static size_t huf_compress_weights(u8* out, const u8* w, u32 wn) {
-    if (wn <= 1) return 0;
+    if (wn <= 1) { EV(HUF_W_WN_LE1); return 0; }
     u32 cnt[13], maxs;
     u32 big = histo(cnt, 13, &maxs, w, wn);
-    if (big == wn) return 1;
-    if (big == 1) return 0;
+    if (big == wn) { EV(HUF_W_RLE); return 1; }
+    if (big == 1) { EV(HUF_W_ALL_DISTINCT); return 0; }
+    EV(HUF_W_FSE);
+    ev_site = 1;
     const u32 tl = fse_opt_log(6, wn, maxs, 2);
     s16 norm[13];
-    if (fse_normalize(norm, tl, cnt, wn, maxs, 0)) return 0;
+    const int bad = fse_normalize(norm, tl, cnt, wn, maxs, 0);
+    if (bad) { ev_site = 0; return 0; }
     size_t h = fse_write_ncount(out, norm, maxs, tl);
+    ev_site = 0;
     fse_ct ct;
     fse_build(&ct, norm, maxs, tl);
     if (wn <= 2) return 0;
@@ -531,6 +567,7 @@ static size_t huf_compress_weights(u8* out, const u8* w, u32 wn) {
     u32 s1, s2;
     int i = (int)wn;
     if (wn & 1) {
+        EV(HUF_W_ODD_COUNT);
         s1 = fse_init_state(&ct, w[--i]);
         s2 = fse_init_state(&ct, w[--i]);
         fse_encode(&b, &ct, &s1, w[--i]);
@@ -552,8 +589,10 @@ static long huf_write_table(u8* out, const huf_ct* ct, u32 maxs, u32 tlog) {
     u8 w[256];
     for (u32 s = 0; s < maxs; s++) w[s] = ct->nb[s] ? (u8)(tlog + 1 - ct->nb[s]) : 0;
     size_t h = huf_compress_weights(out + 1, w, maxs);
-    if (h > 1 && h < maxs / 2) { out[0] = (u8)h; return (long)h + 1; }
-    if (maxs > 128) return -1;
+    if (h > 1 && h < maxs / 2) { EV(HUF_TABLE_FSE); out[0] = (u8)h; return (long)h + 1; }
+    if (h > 1) EV(HUF_W_FSE_TOO_LARGE);
+    if (maxs > 128) { EV(HUF_TABLE_REFUSED); return -1; }
+    EV(HUF_TABLE_DIRECT);
     out[0] = (u8)(128 + maxs - 1);
     w[maxs] = 0;
     for (u32 s = 0; s < maxs; s += 2) out[s / 2 + 1] = (u8)((w[s] << 4) + w[s + 1]);
@@ -575,6 +614,7 @@ static size_t huf_streams(u8* out, const u8* s, size_t n, const huf_ct* ct, int 
     for (int k = 0; k < 4; k++) {
         const size_t len = k < 3 ? seg : n - 3 * seg;
         const size_t c = huf_stream(out + o, s + k * seg, len, ct);
+        if (c > 65535) EV(LIT_STREAM_GT_65535);
         if (c == 0 || c > 65535) return 0;
         if (k < 3) wr16(out + 2 * k, (u32)c);
         o += c;
@@ -595,37 +635,51 @@ static long huf_compress(u8* out, const u8* src, size_t n, int four, huf_state* 
         u32 m1, m2;
         size_t big = histo(cnt, 256, &m1, src, 4096);
         big += histo(cnt, 256, &m2, src + n - 4096, 4096);
-        if (big <= ((2 * 4096) >> 7) + 4) return 0;
+        if (big <= ((2 * 4096) >> 7) + 4) { EV(LIT_SAMPLED_RAW); return 0; }
+        EV(LIT_SAMPLED_PASSED);
     }
     const u32 big = histo(cnt, 256, &maxs, src, n);
-    if (big == n) { out[0] = src[0]; return 1; }
-    if (big <= (n >> 7) + 4) return 0;
+    if (big == n) { EV(LIT_RLE); out[0] = src[0]; return 1; }
+    if (big <= (n >> 7) + 4) { EV(LIT_FLAT_RAW); return 0; }
     int repeat = prev->repeat;
-    if (repeat && !huf_valid(&prev->ct, cnt, maxs)) repeat = 0;
+    if (repeat && !huf_valid(&prev->ct, cnt, maxs)) { EV(LIT_REPEAT_INVALID); repeat = 0; }
     const int preferRepeat = n <= 1024;
     if (preferRepeat && repeat) {
+        EV(LIT_REPEAT_SMALL_DIRECT);
         *reused = 1;
         size_t c = huf_streams(out, src, n, &prev->ct, four);
-        return (c == 0 || c >= n - 1) ? 0 : (long)c;
+        if (c == 0 || c >= n - 1) { EV(LIT_RAW_STREAMS_OLD); return 0; }
+        return (long)c;
     }
     huf_ct fresh;
-    const u32 tl = huf_build(&fresh, cnt, maxs, fse_opt_log(11, n, maxs, 1));
+    const u32 maxNb = fse_opt_log(11, n, maxs, 1);
+    if (ev_c) {     /* which term of FSE_optimalTableLog_internal decided (fse_compress.c:365-377) */
+        const u32 srcBits = hb32((u32)(n - 1)) - 1, mb = fse_min_log(n, maxs);
+        EVK(HUF_MAXNB_5, maxNb - 5);
+        if (mb > (srcBits < 11 ? srcBits : 11)) { if (mb < 5) EV(HUF_MAXNB_BY_FLOOR5); else EV(HUF_MAXNB_BY_MINBITS); }
+        else if (srcBits < 11) { if (srcBits < 5) EV(HUF_MAXNB_BY_FLOOR5); else EV(HUF_MAXNB_BY_SRCSIZE); }
+        else EV(HUF_MAXNB_BY_MAX11);
+    }
+    const u32 tl = huf_build(&fresh, cnt, maxs, maxNb);
     u8 hdr[256];
     const long h = huf_write_table(hdr, &fresh, maxs, tl);
     if (h < 0) return -1;
     if (repeat) {
         const size_t oldS = huf_estimate(&prev->ct, cnt, maxs), newS = huf_estimate(&fresh, cnt, maxs);
         if (oldS <= (size_t)h + newS || (size_t)h + 12 >= n) {
+            if (oldS <= (size_t)h + newS) EV(LIT_REPEAT_OLD_BY_ESTIMATE); else EV(LIT_REPEAT_OLD_BY_H12);
             *reused = 1;
             size_t c = huf_streams(out, src, n, &prev->ct, four);
-            return (c == 0 || c >= n - 1) ? 0 : (long)c;
+            if (c == 0 || c >= n - 1) { EV(LIT_RAW_STREAMS_OLD); return 0; }
+            return (long)c;
         }
+        EV(LIT_REPEAT_NEW_TABLE);
     }
-    if ((size_t)h + 12 >= n) return 0;
+    if ((size_t)h + 12 >= n) { EV(LIT_RAW_H12); return 0; }
     memcpy(out, hdr, (size_t)h);
     next->ct = fresh;
     size_t c = huf_streams(out + h, src, n, &fresh, four);
-    if (c == 0 || (size_t)h + c >= n - 1) return 0;
+    if (c == 0 || (size_t)h + c >= n - 1) { EV(LIT_RAW_STREAMS_NEW); return 0; }
     return h + (long)c;
 }
 
@@ -647,8 +701,14 @@ static size_t lit_rle(u8* out, u8 b, size_t n) {
     return fl + 1;
 }
 static size_t compress_literals(u8* out, const u8* src, size_t n, huf_state* prev, huf_state* next, int disable,
-                                int suspect) {
+                                int suspect, int* new_table) {
     *next = *prev;
+    if (disable) EV(LIT_OFF);
+    else {
+        if (n <= 63) EV(LIT_GATE_LE63);
+        if (n == 63) EV(LIT_GATE_63);
+        if (n == 64) EV(LIT_GATE_64);
+    }
     if (disable || n <= 63) return lit_raw(out, src, n);
     const size_t lh = 3 + (n >= 1024) + (n >= 16 * 1024);
     const int single = n < 256;
@@ -656,10 +716,16 @@ static size_t compress_literals(u8* out, const u8* src, size_t n, huf_state* pre
     huf_state tmp = *prev;
     const long c = huf_compress(out + lh, src, n, !single, prev, &tmp, &reused, suspect);
     const size_t minGain = (n >> 6) + 2;
-    if (c <= 0 || (size_t)c >= n - minGain) { *next = *prev; return lit_raw(out, src, n); }
+    if (c <= 0 || (size_t)c >= n - minGain) {
+        if (c > 0) EV(LIT_RAW_MINGAIN);
+        *next = *prev;
+        return lit_raw(out, src, n);
+    }
     if (c == 1) { *next = *prev; return lit_rle(out, src[0], n); }
+    EVK(LIT_HDR_3, lh - 3);
+    if (single) EV(LIT_STREAMS_1); else EV(LIT_STREAMS_4);
     u32 htype = 3;                         /* set_repeat */
-    if (!reused) { htype = 2; next->ct = tmp.ct; next->repeat = 1; }
+    if (!reused) { htype = 2; next->ct = tmp.ct; next->repeat = 1; *new_table = 1; }
     if (lh == 3) wr24(out, htype + ((u32)(!single) << 2) + ((u32)n << 4) + ((u32)c << 14));
     else if (lh == 4) wr32(out, htype + (2u << 2) + ((u32)n << 4) + ((u32)c << 18));
     else { wr32(out, htype + (3u << 2) + ((u32)n << 4) + ((u32)c << 22)); out[4] = (u8)(c >> 10); }
@@ -689,7 +755,14 @@ static size_t encode_sequences(u8* out, const zseq* seq, size_t nbSeq) {
         llc[i] = (u8)ll_code(seq[i].ll);
         ofc[i] = (u8)hb32(seq[i].off);
         mlc[i] = (u8)ml_code(seq[i].ml - 3);
+        if (seq[i].ll >= 65536) EV(SEQ_LL_GE65536);
+        if (seq[i].ml >= 65539) EV(SEQ_ML_GE65539);
+        if (ofc[i] >= 17) EV(SEQ_OFCODE_GE17);
     }
+    if (nbSeq % 64 < 6) EVK(SEQ_NS_MOD64_0, nbSeq % 64);
+    if (nbSeq == 1) EV(SEQ_NS_1);
+    if (nbSeq >= 63 && nbSeq <= 65) EVK(SEQ_NS_63, nbSeq - 63);
+    if (nbSeq == 128 || nbSeq == 129) EVK(SEQ_NS_128, nbSeq - 128);
     fse_ct ct[3];   /* (on the stack: the _mt chunk loops call this from several threads) */
     const u8* codes[3] = {llc, ofc, mlc};
     const u32 maxTab[3] = {35, 31, 52}, fseLog[3] = {9, 8, 9}, defLog[3] = {6, 5, 6}, defMax[3] = {35, 28, 52};
@@ -703,12 +776,20 @@ static size_t encode_sequences(u8* out, const zseq* seq, size_t nbSeq) {
         const int defOk = t == 1 ? (maxs <= 28) : 1;
         const int ty = select_type(big, nbSeq, defLog[t], defOk);
         types[t] = (u32)ty;
+        if (!defOk) EVT(TYPE_DEFAULT_REFUSED, t);
+        if (ty == 1) EVT(TYPE_RLE, t);
+        else if (ty == 2) EVT(TYPE_FSE, t);
+        else if (big == nbSeq) EVT(TYPE_RLE_AS_PREDEF, t);
+        else if (nbSeq < (((size_t)(1u << defLog[t]) * 9) >> 3)) EVT(TYPE_PREDEF_BY_COUNT, t);
+        else EVT(TYPE_PREDEF_BY_FLATNESS, t);
         if (ty == 1) { fse_build_rle(&ct[t], maxs); *op++ = codes[t][0]; }
         else if (ty == 0) fse_build(&ct[t], defNorm[t], defMax[t], defLog[t]);
         else {
             size_t n1 = nbSeq;
             const u32 tl = fse_opt_log(fseLog[t], nbSeq, maxs, 2);
-            if (cnt[codes[t][nbSeq - 1]] > 1) { cnt[codes[t][nbSeq - 1]]--; n1--; }
+            EVK(TLOG_5, ORACLE_ZSE_TAB_STRIDE * t + (int)tl - 5);
+            if (cnt[codes[t][nbSeq - 1]] > 1) { EVT(LAST_COUNT_TAKEN, t); cnt[codes[t][nbSeq - 1]]--; n1--; }
+            else EVT(LAST_COUNT_NOT, t);
             s16 norm[64];
             fse_normalize(norm, tl, cnt, n1, maxs, n1 >= 2048);
             const size_t h = fse_write_ncount(op, norm, maxs, tl);
@@ -728,6 +809,10 @@ static size_t encode_sequences(u8* out, const zseq* seq, size_t nbSeq) {
     bw_add(&b, seq[L].ll, LLB[llc[L]]);
     bw_add(&b, seq[L].ml - 3, MLB[mlc[L]]);
     bw_add(&b, seq[L].off, ofc[L]);
+    size_t at = b.pos * 8 + b.nb;            /* bits of the stream so far: one sequence's share drives no branch of
+                                                the reference, only how wide a window a parallel writer needs */
+    if (at >= 32) EV(SEQ_BITS_GE32);
+    if (at >= 57) EV(SEQ_BITS_GE57);
     for (size_t n = nbSeq - 1; n-- > 0;) {
         fse_encode(&b, &ct[1], &sOF, ofc[n]);
         fse_encode(&b, &ct[2], &sML, mlc[n]);
@@ -735,6 +820,9 @@ static size_t encode_sequences(u8* out, const zseq* seq, size_t nbSeq) {
         bw_add(&b, seq[n].ll, LLB[llc[n]]);
         bw_add(&b, seq[n].ml - 3, MLB[mlc[n]]);
         bw_add(&b, seq[n].off, ofc[n]);
+        if (b.pos * 8 + b.nb - at >= 32) EV(SEQ_BITS_GE32);
+        if (b.pos * 8 + b.nb - at >= 57) EV(SEQ_BITS_GE57);
+        at = b.pos * 8 + b.nb;
     }
     bw_add(&b, sML, ct[2].tlog);
     bw_add(&b, sOF, ct[1].tlog);
@@ -880,7 +968,7 @@ size_t oracle_zstd_bound(size_t n) {
     return n + (n >> 8) + (n < (128u << 10) ? ((128u << 10) - n) >> 11 : 0);
 }
 
-int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int level) {
+static int64_t zstd_compress_body(const uint8_t* src, size_t n, uint8_t* dst, int level) {
     zparams P;
     if (get_params(level, n, &P)) return -1;
     u8* op = dst;
@@ -919,7 +1007,7 @@ int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int lev
     zseq* seq = (zseq*)malloc((bsize / 3 + 16) * sizeof(zseq));
     u8* lits = (u8*)malloc(bsize + 16);
     u8* body = (u8*)malloc(bsize * 2 + 1024);
-    int first = 1;
+    int first = 1, confirmed = 1;
     for (size_t bs = 0; bs < n; bs += bsize) {
         const size_t be = bs + bsize < n ? bs + bsize : n;
         const size_t len = be - bs;
@@ -927,24 +1015,31 @@ int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int lev
         size_t csize = 0;
         u32 nrep[2] = {rep[0], rep[1]};
         huf_state hnext = hprev;
+        int new_table = 0;
         if (len >= 7) {   /* MIN_CBLOCK_SIZE + ZSTD_blockHeaderSize + 1 */
             size_t ns = 0, nl = 0;
             fast_block(&m, bs, be, nrep, stepSize, wsz, seq, &ns, lits, &nl);
             const int suspect = ns == 0 || nl / ns >= 20;
+            if (ns && nl / ns == 19) EV(LIT_SUSPECT_19);
+            if (ns && nl / ns == 20) EV(LIT_SUSPECT_20);
             u8* o = body;
-            o += compress_literals(o, lits, nl, &hprev, &hnext, litDisabled, suspect);
+            o += compress_literals(o, lits, nl, &hprev, &hnext, litDisabled, suspect, &new_table);
             if (ns < 128) *o++ = (u8)ns;
             else if (ns < 0x7F00) { o[0] = (u8)((ns >> 8) + 0x80); o[1] = (u8)ns; o += 2; }
             else { o[0] = 0xFF; wr16(o + 1, (u32)(ns - 0x7F00)); o += 3; }
             if (ns) {
                 const size_t s = encode_sequences(o, seq, ns);
                 csize = s ? (size_t)(o - body) + s : 0;
+                if (!s) EV(BLOCK_RAW_SEQUENCES_FAILED);
             } else {
                 csize = (size_t)(o - body);
             }
-            if (csize && csize >= len - ((len >> 6) + 2)) csize = 0;      /* ZSTD_minGain */
-        }
-        if (len >= 7 && !first && csize < 25 && is_rle(src + bs, len)) csize = 1;
+            if (csize && csize >= len - ((len >> 6) + 2)) { EV(BLOCK_RAW_MINGAIN); csize = 0; }      /* ZSTD_minGain */
+        } else EV(BLOCK_LEN_LT7);
+        if (len >= 7 && first && csize < 25 && is_rle(src + bs, len)) EV(BLOCK_RLE_REFUSED_FIRST);
+        if (len >= 7 && !first && csize < 25 && is_rle(src + bs, len)) { EV(BLOCK_RLE); csize = 1; }
+        if (!first) { if (confirmed) EV(BLOCK_REPCODES_CONFIRMED); else EV(BLOCK_REPCODES_UNCONFIRMED); }
+        confirmed = csize > 1;               /* (what the next block starts from) */
         if (csize == 0) {
             wr24(op, (u32)last + (u32)(len << 3));
             memcpy(op + 3, src + bs, len);
@@ -958,10 +1053,23 @@ int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int lev
             memcpy(op + 3, body, csize);
             op += 3 + csize;
             rep[0] = nrep[0]; rep[1] = nrep[1];      /* confirm repcodes + entropy tables */
+            if (new_table) EV(BLOCK_CMP_NEW_HUF_KEPT);
             hprev = hnext;
         }
         first = 0;
     }
     free(m.table); free(seq); free(lits); free(body);
     return (int64_t)(op - dst);
+}
+
+int64_t oracle_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, int level) {
+    return zstd_compress_body(src, n, dst, level);
+}
+
+int64_t oracle_zstd_compress_census(const uint8_t* src, size_t n, uint8_t* dst, int level, uint64_t* c) {
+    ev_c = c;
+    ev_site = 0;
+    const int64_t r = zstd_compress_body(src, n, dst, level);
+    ev_c = NULL;
+    return r;
 }

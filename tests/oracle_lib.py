@@ -35,6 +35,12 @@ def oracle():
         L.oracle_lz4_decompress_safe.argtypes = [_P, C.c_int, _P, C.c_int]
         L.oracle_snappy_compress.restype = _SZ
         L.oracle_snappy_compress.argtypes = [_P, _SZ, _P]
+        L.oracle_zstd_compress.restype = _I64
+        L.oracle_zstd_compress.argtypes = [_P, _SZ, _P, C.c_int]
+        L.oracle_zstd_compress_census.restype = _I64
+        L.oracle_zstd_compress_census.argtypes = [_P, _SZ, _P, C.c_int, _P]
+        L.oracle_zstd_bound.restype = _SZ
+        L.oracle_zstd_bound.argtypes = [_SZ]
         L.oracle_snappy_bound.restype = _SZ
         L.oracle_snappy_bound.argtypes = [_SZ]
         L.oracle_snappy_uncompress.restype = _I64
@@ -150,6 +156,31 @@ def snappy_compress_census(data: np.ndarray):
     c = np.zeros(64, np.uint64)
     r = L.oracle_snappy_compress_census(data.ctypes.data, len(data), out.ctypes.data, c.ctypes.data)
     return out[:r].tobytes(), c
+
+
+def zstd_compress_census(data: np.ndarray, level: int = 1):
+    """(frame, counters) of oracle_zstd_compress_census: one chunk's frame as oracle_zstd_compress writes it (no
+    raw-store rule) and the entropy stage's event counts, in the order of oracle.h's ORACLE_ZSE_*
+    (tests/zstd_entropy_census.py names them)"""
+    L = oracle()
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    src = data if len(data) else np.zeros(1, np.uint8)
+    out = np.zeros(L.oracle_zstd_bound(len(data)) + 64, np.uint8)
+    c = np.zeros(256, np.uint64)
+    r = L.oracle_zstd_compress_census(src.ctypes.data, len(data), out.ctypes.data, level, c.ctypes.data)
+    assert r > 0, (r, level)
+    return out[:r].tobytes(), c
+
+
+def zstd_compress(data: np.ndarray, level: int = 1) -> bytes:
+    """one chunk's frame as oracle_zstd_compress writes it (no raw-store rule)"""
+    L = oracle()
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    src = data if len(data) else np.zeros(1, np.uint8)
+    out = np.zeros(L.oracle_zstd_bound(len(data)) + 64, np.uint8)
+    r = L.oracle_zstd_compress(src.ctypes.data, len(data), out.ctypes.data, level)
+    assert r > 0, (r, level)
+    return out[:r].tobytes()
 
 
 def compress_chunks(data: np.ndarray, codec: str, chunk: int, level: int = 1, use_ref=None, threads: int = 0):

@@ -24,6 +24,11 @@ raw), block 2 the same bytes with 0xFF over every 17th and over the last 64.  Th
 block's second byte (the first 255 positions of a block are all indexed), every later one is the repeat offset
 checked two bytes past the 0xFF, extended back by the one byte the finder allows: 7708 literals, all 0xFF.
 
+This census reads frame headers only: it cannot see why a literals section is raw, whether the Huffman depth limiter
+or the secondary normalisation ran, whether a kept table was reused by the 1024-byte shortcut or by the estimate, or
+which remainder of the 64-sequence rounds a block has.  tests/zstd_entropy_census.py counts those decisions in the
+restatement itself, and tests/zstd_entropy_inputs.py reaches them (importing rows of this file where they already do).
+
 Not reached from the compressor:
   lit/rle/hdr1   unreachable by construction: ZSTD_compressLiterals stores 63 literals and fewer raw, and the
                  1-byte header holds sizes up to 31 (the decoder's branch: a hand-built frame,
