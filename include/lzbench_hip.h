@@ -644,6 +644,63 @@ int lzh_debug_zstd_dfast_dict_params(int level, size_t n, size_t dict_bytes, uin
 long lzh_debug_zstd_dfast_dict_parse(int level, const void* dict, size_t dict_bytes, const void* src, size_t n,
                                      uint32_t* seqs, size_t cap, uint64_t* events);
 
+/* ---- 3i. ragged LZ4 frames -------------------------------------------------------------------- */
+/* lzh_compress_ragged_async / lzh_decompress_ragged_async for LZ4 frames (LZH_CODEC_LZ4F above), under names of their
+ * own: one self-describing frame per chunk, what the lz4 tool and every LZ4 binding read.  The five functions of 3b
+ * keep refusing LZH_CODEC_LZ4F and LZH_CODEC_NVLZ4; the nvcomp container has no ragged call.
+ * What stays as 3b: d_in_ptrs, d_in_bytes, d_out_ptrs and d_out_bytes are device arrays of nchunks entries; chunk i is
+ * the d_in_bytes[i] bytes at d_in_ptrs[i], any alignment; chunks may overlap or repeat; every input chunk needs 16
+ * readable bytes after it; max_chunk_bytes at most 16 MiB, else LZH_EARG; nchunks == 0 returns LZH_OK and launches
+ * nothing; a chunk whose device-side size passes max_chunk_bytes is not processed -- d_csizes[i] = 0 (it takes no
+ * packed bytes) or d_status[i] = -1, and no kernel touches a slot for it; packed_cap is enforced on the device -- a
+ * frame whose packed range would pass it is not written, d_csizes and d_offsets still report every size, and
+ * d_offsets[nchunks] > packed_cap tells the caller that the output is incomplete; d_offsets of the decompress call may
+ * be NULL (derived from d_csizes into d_temp); the raw-store rule holds on both sides, at frame level (a frame whose
+ * size equals its chunk's is stored raw, and decoded as raw); every launch goes on hip_stream, with no side stream,
+ * event, host synchronisation or size read back, so the calls can be captured in a stream.
+ * Check order, all before any device call:
+ *   1. level and max_chunk_bytes: LZH_EARG;
+ *   2. nchunks == 0: LZH_OK;
+ *   3. a null pointer (every pointer but hip_stream and the decompress call's d_offsets): LZH_EARG;
+ *   4. the launch grid -- nchunks x the blocks per frame of max_chunk_bytes (compress: ceil(max_chunk_bytes / min(block
+ *      size, max_chunk_bytes)), at least 1; decompress: ceil(max_chunk_bytes / 64 KiB), at least 1) must stay within
+ *      0x7fffffff: LZH_EARG;
+ *   5. temp_bytes below the sizing answer: LZH_ESPACE.
+ * The three sizing functions are host arithmetic, non-decreasing in max_chunk_bytes and nchunks (total_in_bytes and
+ * nchunks), and the two temp answers are 0 exactly where the calls return LZH_EARG for those arguments.
+ * level: LZH_LZ4F_PARAMS(blockSizeID 0 | 4 .. 7, flags, acceleration), accepted exactly where
+ * lzh_level_supported(LZH_CODEC_LZ4F, level, .) is 1 and LZH_LZ4F_LINKED is not set.  Linked-block compression is
+ * not built here: with the flag the call returns LZH_EARG (the uniform call has the one-wave-per-frame linked kernel).
+ * Compressed bytes: frame i is exactly what lzh_compress_async(LZH_CODEC_LZ4F, level, .., n = d_in_bytes[i],
+ * chunk_size >= n) writes for that chunk alone, i.e. LZ4F_compressFrame with independent blocks: the header's
+ * block-size id follows LZ4F_optimalBSID for the chunk's own size; content size, block checksums and content checksum
+ * follow the flags; a block that LZ4 does not shrink is stored raw.  Equal sizes over contiguous input give the uniform
+ * call's d_csizes, d_offsets and packed bytes.  A zero-length chunk is legal: the 11-byte frame (header, end mark), 15
+ * bytes with a content checksum.  lzh_lz4f_ragged_max_packed_bytes is the capacity no batch of that total size and
+ * chunk count exceeds.
+ * Decoding: d_status[i] and the output bytes are those of lzh_decompress_async(LZH_CODEC_LZ4F, ..) for that frame and
+ * n = chunk_size = d_out_bytes[i]: the decoded size, -1 malformed, -2 a feature outside the supported set (a frame
+ * that does not decode to exactly d_out_bytes[i] bytes gets one of the two).  Independent and linked frames decode
+ * alike.  An empty frame decodes to status 0 and writes nothing.  Output pointers of any alignment; nothing is written
+ * past d_out_ptrs[i] + d_out_bytes[i].
+ * Temp, compress: uniform slots.  With B the level's block size, bs = min(B, max_chunk_bytes) and bpf =
+ * ceil(max_chunk_bytes / bs), every frame has bpf block slots; a block takes a staging slot, a sequence-record slot, a
+ * record header, two u32 (its size, its offset in the frame) and 16 bytes of the block table (its pointer and size).  A
+ * skewed batch therefore pays for its largest chunk nchunks times: 4096 chunks of which one has 16 MiB size as 4096
+ * chunks of 16 MiB.  A compact layout is not built; the block table is what it would re-place (block slots from a scan
+ * of per-chunk block counts).  Temp, decompress: scanned offsets, nchunks x ceil(max_chunk_bytes / 64 KiB) 32-byte
+ * block descriptors and block statuses, nchunks frame statuses. */
+size_t lzh_lz4f_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_lz4f_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks);
+size_t lzh_lz4f_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks);
+int lzh_lz4f_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                   size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                   uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream);
+int lzh_lz4f_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                     const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                     size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                     size_t temp_bytes, void* hip_stream);
+
 /* Dispatch the stages of lzh_compress_async separately (profiling / roofline): the codec
  * kernel alone writes the staging slots and per-chunk sizes. */
 int lzh_compress_kernel_only(int codec, int level, const void* d_in, size_t n, size_t in_readable,

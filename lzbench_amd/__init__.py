@@ -102,6 +102,7 @@ SIGNATURES = {
     "lzh_decompress_async": (C.c_int, [C.c_int, _P, _SZ, _P, _P, _SZ, _SZ, _P, _P, _P, _SZ, _P]),
     "lzh_ragged_max_packed_bytes": (_SZ, [C.c_int, _SZ, _SZ]),
     "lzh_zstd_ragged_max_packed_bytes": (_SZ, [_SZ, _SZ]),
+    "lzh_lz4f_ragged_max_packed_bytes": (_SZ, [_SZ, _SZ]),
     "lzh_debug_zstd_ragged_split_layout": (C.c_int, [_SZ, _SZ, _P]),
     "lzh_debug_zstd_ragged_split_compact_slots": (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     "lzh_debug_zstd_ragged_split_compact_layout": (C.c_int, [_SZ, _SZ, _SZ, _P]),
@@ -120,7 +121,7 @@ SIGNATURES = {
     "lzh_version": (C.c_char_p, []),
     "lzh_debug_zstd_dfast_dict_params": (C.c_int, [C.c_int, _SZ, _SZ, _P]),
     "lzh_debug_zstd_dfast_dict_parse": (C.c_long, [C.c_int, _P, _SZ, _P, _SZ, _P, _SZ, _P]),
-    # the ragged async calls of 3b .. 3h and their *_temp_bytes functions: generated from the table
+    # the ragged async calls of 3b .. 3i and their *_temp_bytes functions: generated from the table
     **ragged_calls.signatures(),
 }
 
@@ -434,6 +435,12 @@ class RaggedCodec:
     zstd_dfast_dict (a name of RaggedCodec's alone; level 3 and a dictionary, else ValueError) is level 3 with that
     dictionary (include/lzbench_hip.h 3h): the limits, the refusals and the decoder of the paragraph above, compress()
     writing what ZSTD_compress_usingDict writes at level 3.  zstd and zstd_dfast keep refusing level 3 with a dictionary.
+    lz4frame (level = an LZH_LZ4F_PARAMS value: block-size id 0 | 4 .. 7, the LZ4F_* flags, acceleration << 8) writes one
+    LZ4 frame per chunk with independent blocks (include/lzbench_hip.h 3i): the bytes DeviceCodec("lz4frame") writes
+    for a chunk size that holds the chunk, a zero-length chunk the 11-byte frame.  A level with LZ4F_LINKED is refused
+    with ValueError (linked-block compression is the uniform call's), so are compact, compact_scratch, split_decode,
+    compact_decode and a dictionary.  decompress() takes independent and linked frames alike.  Every frame has the
+    block slots of max_chunk_bytes: a skewed batch pays for its largest chunk max_chunks times.
     Work is queued on torch's current stream; nothing synchronises with the host.
     """
 
@@ -472,6 +479,11 @@ class RaggedCodec:
         if compact_decode and dictionary is not None:
             raise ValueError("ragged batches: a zstd dictionary goes with the one-wave decoder (no compact_decode)")
         self.compact_decode = compact_decode
+        lz4f = self.codec == LZH_CODEC_LZ4F
+        if lz4f and (compact or dictionary is not None):
+            raise ValueError("ragged batches: lz4frame goes with the uniform-slot layout and no dictionary")
+        if lz4f and level & LZ4F_LINKED:
+            raise ValueError("ragged batches: lz4frame compresses independent blocks (no LZ4F_LINKED in the level)")
         zdict = dictionary is not None and codec in ("zstd", "zstd_fast", "zstd_dfast_dict")
         if zdict and (compact_scratch or split_decode):
             raise ValueError("ragged batches: a zstd dictionary goes with the uniform-slot layout and the one-wave decoder "
@@ -482,7 +494,7 @@ class RaggedCodec:
         # the variant, chosen once: a compress and a decompress row of ragged_calls.RAGGED_CALLS (zstd_dfast decodes with
         # zstd's), and the values their heads and sizing calls pick from by name
         family = ("zstd_dict" if zdict else "zstd_dfast" if dfast else "zstd" if self.zstd
-                  else "lz4_dict" if dictionary is not None else "lz")
+                  else "lz4_dict" if dictionary is not None else "lz4f" if lz4f else "lz")
         # (3h compresses through its own call and decodes through 3f's)
         self._crec = ragged_calls.COMPRESS["zstd_dfast_dict" if dfdict else family, compact or compact_scratch]
         self._drec = ragged_calls.DECOMPRESS["zstd" if dfast else family, compact_decode]
@@ -512,6 +524,8 @@ class RaggedCodec:
             self._head["dict"] = self.dictionary.data_ptr()
         if self.zstd:
             self.max_packed = L.lzh_zstd_ragged_max_packed_bytes(self.max_total, max_chunks)
+        elif lz4f:
+            self.max_packed = L.lzh_lz4f_ragged_max_packed_bytes(self.max_total, max_chunks)
         else:
             self.max_packed = L.lzh_ragged_max_packed_bytes(self.codec, self.max_total, max_chunks)
         self.packed = torch.empty(self.max_packed + 64, **u8)

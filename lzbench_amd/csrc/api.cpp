@@ -343,6 +343,10 @@ static hipError_t launch_pack(const LzhBatch& B, const LzhCompactSlots& S, const
                               uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
     return lzh_launch_pack_compact(B, S, csizes, offsets, packed, packed_cap, s);
 }
+static hipError_t launch_pack(const LzhBatch& B, const LzhRaggedFrame& R, const uint32_t* csizes, const uint64_t* offsets,
+                              uint8_t* packed, uint64_t packed_cap, hipStream_t s) {
+    return lzh_launch_lz4f_pack_ragged(B, R, csizes, offsets, packed, packed_cap, s);
+}
 
 // The ragged compress calls (3b .. 3h; uniform slots, compact layout): the argument checks in their order (ok: the
 // codec / level takes max_chunk_bytes; have_dict: the dictionary's pointer, true for a call without one; grid_factor:
@@ -372,16 +376,17 @@ static int ragged_compress(bool ok, bool have_dict, size_t grid_factor, const Te
     return LZH_OK;
 }
 
-// The two ragged decompress calls: the argument checks in their order, the temp of ragged_decode_temp, then
-// decode(offs, t) with the caller's offsets or, without them, the ones scanned into temp.
+// The ragged decompress calls: the argument checks in their order (grid_factor: launch blocks per chunk; t: the call's
+// layout, its total the temp needed, the scanned offsets at t.scan), then decode(offs, t) with the caller's offsets or,
+// without them, the ones scanned into temp.
 template <class Decode>
-static int ragged_decompress(bool ok, size_t nchunks, bool pointers, const uint32_t* d_csizes, const uint64_t* d_offsets,
-                             void* d_temp, size_t temp_bytes, hipStream_t s, Decode decode) {
+static int ragged_decompress(bool ok, size_t nchunks, size_t grid_factor, const DecodeTemp& t, bool pointers,
+                             const uint32_t* d_csizes, const uint64_t* d_offsets, void* d_temp, size_t temp_bytes,
+                             hipStream_t s, Decode decode) {
     if (!ok) return LZH_EARG;
     if (nchunks == 0) return LZH_OK;
     if (!pointers) return LZH_EARG;
-    if (nchunks > 0x7fffffffu) return LZH_EARG;
-    const DecodeTemp t = ragged_decode_temp(nchunks);
+    if (nchunks * grid_factor > 0x7fffffffu) return LZH_EARG;   // launch grids
     if (temp_bytes < t.total) return LZH_ESPACE;
     Range range("lzh:decompress");
     const uint64_t* offs = d_offsets;
@@ -445,8 +450,9 @@ int lzh_decompress_ragged_async(int codec, const void* d_packed, size_t packed_r
                                 size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     return ragged_decompress(
-        ragged_ok(codec, max_chunk_bytes), nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
-        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp& t) {
+        ragged_ok(codec, max_chunk_bytes), nchunks, 1, ragged_decode_temp(nchunks),
+        d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp, temp_bytes, s,
+        [&](const uint64_t* offs, const DecodeTemp& t) {
             void* desc = (uint8_t*)d_temp + t.desc;
             const hipError_t e = lzh_launch_ragged_desc(offs, d_csizes, d_out_ptrs, d_out_bytes, max_chunk_bytes, desc,
                                                         d_status, (uint32_t)nchunks, s);
@@ -492,7 +498,7 @@ int lzh_lz4_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes, 
                                          void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     return ragged_decompress(
-        lz4_dict_ok(dict_bytes, max_chunk_bytes), nchunks,
+        lz4_dict_ok(dict_bytes, max_chunk_bytes), nchunks, 1, ragged_decode_temp(nchunks),
         d_dict && d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp,
         temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
             return lzh_launch_lz4_dict_decompress((const uint8_t*)d_dict, (uint32_t)dict_bytes, (const uint8_t*)d_packed,
@@ -544,7 +550,7 @@ int lzh_zstd_decompress_ragged_dict_async(const void* d_dict, size_t dict_bytes,
                                           void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     return ragged_decompress(
-        zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes), nchunks,
+        zstd_dict_sizes_ok(dict_bytes, max_chunk_bytes), nchunks, 1, ragged_decode_temp(nchunks),
         d_dict && d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp,
         temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
             return lzh_launch_zstd_dict_decompress((const uint8_t*)d_dict, (uint32_t)dict_bytes, (const uint8_t*)d_packed,
@@ -664,8 +670,9 @@ int lzh_zstd_decompress_ragged_async(const void* d_packed, size_t packed_readabl
                                      size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     return ragged_decompress(
-        max_chunk_bytes <= kLz4SplitMax, nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
-        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+        max_chunk_bytes <= kLz4SplitMax, nchunks, 1, ragged_decode_temp(nchunks),
+        d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp, temp_bytes, s,
+        [&](const uint64_t* offs, const DecodeTemp&) {
             // with room for it the split decoder's layout lives in temp (the offsets at the same place); with less
             // every frame is decoded whole by one wave
             const ZstdRaggedSplitTemp z = zstd_ragged_split_temp(nchunks, max_chunk_bytes);
@@ -727,8 +734,9 @@ int lzh_zstd_decompress_ragged_split_compact_async(const void* d_packed, size_t 
                                                    size_t temp_bytes, void* hip_stream) {
     hipStream_t s = (hipStream_t)hip_stream;
     return ragged_decompress(
-        max_chunk_bytes <= kLz4SplitMax, nchunks, d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp,
-        d_csizes, d_offsets, d_temp, temp_bytes, s, [&](const uint64_t* offs, const DecodeTemp&) {
+        max_chunk_bytes <= kLz4SplitMax, nchunks, 1, ragged_decode_temp(nchunks),
+        d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp, temp_bytes, s,
+        [&](const uint64_t* offs, const DecodeTemp&) {
             const ZstdRaggedSplitCompactTemp z = zstd_ragged_split_compact_temp(total_out_bytes, max_chunk_bytes, nchunks);
             uint8_t* base = (uint8_t*)d_temp;
             if (z.ok && temp_bytes >= z.total) {
@@ -876,6 +884,62 @@ int lzh_zstd_dfast_compress_ragged_compact_async(int level, const void* const* d
                            [&](const LzhBatch& B, const LzhCompactSlots& S, hipStream_t s) {
                                return lzh_launch_zstd_dfast_compact(B, level, S, d_csizes, s);
                            });
+}
+
+// ---- 3i. ragged LZ4 frames: entry points of their own (the calls of 3b keep refusing both framed codecs), through
+// the skeleton of 3b; lz4f_ragged_temp and lz4f_ragged_decode_temp lay the temp out for the sizing calls and the
+// async calls.  Independent blocks alone: a level with LZH_LZ4F_LINKED is refused ----
+static bool lz4f_ragged_ok(int level, size_t max_chunk_bytes) {
+    return frame_level_ok(LZH_CODEC_LZ4F, level) && !(level & LZH_LZ4F_LINKED) && max_chunk_bytes <= kLz4SplitMax;
+}
+static Lz4fRaggedTemp lz4f_ragged_call_temp(int level, size_t max_chunk_bytes, size_t nchunks) {
+    return lz4f_ragged_temp(level, frame_block_bytes(LZH_CODEC_LZ4F, level), max_chunk_bytes, nchunks);
+}
+
+size_t lzh_lz4f_ragged_compress_temp_bytes(int level, size_t max_chunk_bytes, size_t nchunks) {
+    return lz4f_ragged_ok(level, max_chunk_bytes) ? lz4f_ragged_call_temp(level, max_chunk_bytes, nchunks).total : 0;
+}
+
+size_t lzh_lz4f_ragged_decompress_temp_bytes(size_t max_chunk_bytes, size_t nchunks) {
+    return max_chunk_bytes <= kLz4SplitMax ? lz4f_ragged_decode_temp(nchunks, max_chunk_bytes).total : 0;
+}
+
+size_t lzh_lz4f_ragged_max_packed_bytes(size_t total_in_bytes, size_t nchunks) {
+    // the sum of codec_bound over the chunks, whatever their sizes: 8 bytes per 64 KiB block (a chunk of s bytes has
+    // ceil(s / 64 KiB) at the most, summed: total / 64 KiB + nchunks) and codec_bound(0) per chunk; then the uniform
+    // call's 8 bytes per chunk and 64
+    return total_in_bytes + 8 * (total_in_bytes / 65536 + nchunks) + nchunks * (codec_bound(LZH_CODEC_LZ4F, 0) + 8) + 64;
+}
+
+int lzh_lz4f_compress_ragged_async(int level, const void* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t nchunks,
+                                   size_t max_chunk_bytes, void* d_packed, size_t packed_cap, uint32_t* d_csizes,
+                                   uint64_t* d_offsets, void* d_temp, size_t temp_bytes, void* hip_stream) {
+    const bool ok = lz4f_ragged_ok(level, max_chunk_bytes);
+    const Lz4fRaggedTemp t = ok ? lz4f_ragged_call_temp(level, max_chunk_bytes, nchunks) : Lz4fRaggedTemp{};
+    return ragged_compress(ok, true, t.g.bpf, t, d_in_ptrs, d_in_bytes, nchunks, max_chunk_bytes, d_packed, packed_cap,
+                           d_csizes, d_offsets, d_temp, temp_bytes, hip_stream,
+                           [&](const LzhBatch& B, const LzhRaggedFrame& R, hipStream_t s) {
+                               return lzh_launch_lz4f_ragged(B, std::max(1, (level >> 8) & 0xff), R, d_csizes, s);
+                           });
+}
+
+int lzh_lz4f_decompress_ragged_async(const void* d_packed, size_t packed_readable, const uint32_t* d_csizes,
+                                     const uint64_t* d_offsets, void* const* d_out_ptrs, const uint64_t* d_out_bytes,
+                                     size_t nchunks, size_t max_chunk_bytes, int32_t* d_status, void* d_temp,
+                                     size_t temp_bytes, void* hip_stream) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool ok = max_chunk_bytes <= kLz4SplitMax;
+    const uint32_t mb = ok ? frame_maxbpf(LZH_CODEC_LZ4F, max_chunk_bytes) : 1;
+    return ragged_decompress(
+        ok, nchunks, mb, ok ? lz4f_ragged_decode_temp(nchunks, max_chunk_bytes) : DecodeTemp{},
+        d_packed && d_csizes && d_out_ptrs && d_out_bytes && d_status && d_temp, d_csizes, d_offsets, d_temp, temp_bytes, s,
+        [&](const uint64_t* offs, const DecodeTemp& t) {
+            uint8_t* base = (uint8_t*)d_temp;
+            return lzh_launch_lz4f_decompress_ragged((const uint8_t*)d_packed, packed_readable, offs, d_csizes, d_out_ptrs,
+                                                     d_out_bytes, max_chunk_bytes, d_status, (uint32_t)nchunks, mb,
+                                                     base + t.desc, (int32_t*)(base + t.bstat),
+                                                     (int32_t*)(base + t.fstat), s);
+        });
 }
 
 }  // extern "C"

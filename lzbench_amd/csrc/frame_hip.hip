@@ -27,72 +27,7 @@
 // checksums) writes one 32-byte descriptor per block for the block decoder (decode_hip.hip,
 // descriptor mode); lzh_frame_finish_kernel checks the blocks' results and the content checksum.
 // XXH32 restates /root/reference/lz4/xxhash.c:269-389 as wave-uniform code.
-#include "common.h"
-
-namespace frm {
-
-constexpr uint32_t P1 = 2654435761U, P2 = 2246822519U, P3 = 3266489917U, P4 = 668265263U, P5 = 374761393U;
-__device__ __forceinline__ uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// XXH32 (seed 0) of bytes [0, len) of b, computed by the whole wave: lane j loads 16-byte stripe j
-// of each 1 KiB batch, the four accumulators then take the stripes in order (wave-uniform code)
-__device__ uint32_t xxh32_wave(const Bytes& b, uint32_t len, int lane) {
-    uint32_t h;
-    uint32_t p = 0;
-    if (len >= 16) {
-        uint32_t v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0u - P1;
-        const uint32_t ns = len / 16;   // stripes with p < len - 15, i.e. floor(len / 16)
-        for (uint32_t s0 = 0; s0 < ns; s0 += 64) {
-            const uint32_t q = (s0 + (uint32_t)lane) * 16;
-            const bool in = s0 + (uint32_t)lane < ns;
-            const uint32_t w0 = in ? b.w32(q) : 0, w1 = in ? b.w32(q + 4) : 0, w2 = in ? b.w32(q + 8) : 0,
-                           w3 = in ? b.w32(q + 12) : 0;
-            const uint32_t m = min(64u, ns - s0);
-            for (uint32_t j = 0; j < m; j++) {
-                v1 = rotl(v1 + rdlane(w0, (int)j) * P2, 13) * P1;
-                v2 = rotl(v2 + rdlane(w1, (int)j) * P2, 13) * P1;
-                v3 = rotl(v3 + rdlane(w2, (int)j) * P2, 13) * P1;
-                v4 = rotl(v4 + rdlane(w3, (int)j) * P2, 13) * P1;
-            }
-        }
-        p = ns * 16;
-        h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-    } else {
-        h = P5;
-    }
-    h += len;
-    const uint32_t t = b.w32((int)p), t2 = b.w32((int)p + 4), t3 = b.w32((int)p + 8), t4 = b.w32((int)p + 12);
-    const uint32_t tw[4] = {uni(t), uni(t2), uni(t3), uni(t4)};
-    int k = 0;
-    for (; p + 4 <= len; p += 4, k++) h = rotl(h + tw[k] * P3, 17) * P4;
-    for (; p < len; p++) h = rotl(h + uni(b.b((int)p)) * P5, 11) * P1;   // (bytewise: exact-size views)
-    h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint64_t bsize_of(int id) { return (uint64_t)1 << (8 + 2 * id); }
-
-// LZ4F_optimalBSID (lz4frame.c:304-316); 0 = default = max64KB (lz4frame.c:640-641)
-__device__ __forceinline__ int optimal_bsid(int req, uint64_t n) {
-    int id = 4;
-    uint64_t mb = 64u << 10;
-    while (req > id) {
-        if (n <= mb) return id;
-        id++;
-        mb <<= 2;
-    }
-    return req ? req : 4;
-}
-
-// little-endian byte stores of v at pos (a frame header field at an arbitrary byte offset)
-__device__ __forceinline__ void put_le(const Bytes& o, int pos, uint64_t v, int nb) {
-    for (int i = 0; i < nb; i++) o.st8(pos + i, (uint32_t)(v >> (8 * i)) & 0xffu);
-}
-
-}  // namespace frm
-
-// LZ4F: frame header bytes for frame content size s
-__device__ __forceinline__ int lz4f_header_len(int params, uint64_t s) { return 7 + (((params & 0x40) && s) ? 8 : 0); }
+#include "frame.h"
 
 // one lane per frame: frame sizes (-> csizes[f], raw-store rule applied) and the offsets of the
 // blocks inside their frame (rel[i]: LZ4F = the block's header word, NVLZ4 = its stream)
@@ -226,10 +161,6 @@ lzh_frame_pack_kernel(int codec, int params, const uint8_t* in, uint64_t n_total
 }
 
 // ------------------------------------------------------------------------------------ decoding
-// Block descriptor for the block decoder: u64 source offset in packed, u64 destination offset,
-// u32 stored size, u32 decoded size, u32 flags (1 = stored raw), u32 spare.
-struct FrameDesc { uint64_t src, dst; uint32_t cs, ds, flags, pad; };
-
 // one wave per frame: header checks and block walk (lz4frame.c:1150-1260 LZ4F_decodeHeader,
 // :1384-1899 LZ4F_decompress; nvcomp: LZ4Metadata.cpp:60-110), descriptors for every block
 // (maxbpf slots per frame, unused slots decode nothing), fstat[f] = 0 or a negative status:

@@ -307,3 +307,30 @@ hipError_t lzh_launch_frame_finish(int codec, const uint8_t* packed, const uint6
                                    uint64_t n_total, uint64_t fs, uint32_t maxbpf, const void* desc,
                                    const int32_t* bstat, const int32_t* fstat, const uint8_t* out, int32_t* status,
                                    uint32_t nframes, hipStream_t s);
+
+// ragged LZ4 frames (lz4f_ragged_hip.hip; include/lzbench_hip.h 3i): a frame per chunk of the batch, the frames'
+// blocks laid out for the largest chunk -- blocks of bs = min(the level's block size, max_bytes), bpf = ceil(max_bytes
+// / bs) block slots per frame, frame i's at i * bpf.  F: the slots of nchunks * bpf blocks as frame_temp lays them
+// out; bptrs / bbytes: the derived block batch (nchunks * bpf entries each), written by lzh_launch_lz4f_ragged and
+// handed to lzh_launch_lz4_ragged as a batch with max_bytes = bs; params: the call's level.
+struct LzhRaggedFrame {
+    LzhFrameSlots F;
+    const void** bptrs;
+    uint64_t* bbytes;
+    uint64_t bs;
+    uint32_t bpf;
+    int params;
+};
+// block table -> the ragged LZ4 parse and emit kernels over the blocks (sizes to F.bcs) -> the frame sizes (csizes;
+// 0 for a chunk larger than max_bytes) and the block offsets (F.rel); then, after the scan, the pack: a frame whose
+// packed range would pass packed_cap is not written.  Every launch on s.
+hipError_t lzh_launch_lz4f_ragged(const LzhBatch& B, int acc, const LzhRaggedFrame& R, uint32_t* csizes, hipStream_t s);
+hipError_t lzh_launch_lz4f_pack_ragged(const LzhBatch& B, const LzhRaggedFrame& R, const uint32_t* csizes,
+                                       const uint64_t* offsets, uint8_t* packed, uint64_t packed_cap, hipStream_t s);
+// frame i decodes to out_bytes[i] bytes at out_ptrs[i]: the ragged frame parse (maxbpf descriptor slots per frame at
+// desc, frame statuses at fstat), lzh_launch_decompress over the nchunks * maxbpf descriptors with a null output base
+// (block statuses at bstat), the ragged frame finish.  An out_bytes[i] above max_bytes gives status[i] = -1.
+hipError_t lzh_launch_lz4f_decompress_ragged(const uint8_t* packed, uint64_t packed_readable, const uint64_t* offsets,
+                                             const uint32_t* csizes, void* const* out_ptrs, const uint64_t* out_bytes,
+                                             uint64_t max_bytes, int32_t* status, uint32_t nchunks, uint32_t maxbpf,
+                                             void* desc, int32_t* bstat, int32_t* fstat, hipStream_t s);

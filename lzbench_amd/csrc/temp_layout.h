@@ -164,6 +164,37 @@ static inline FrameTemp frame_temp(const FrameGeo& g) {
     return t;
 }
 
+// ---- ragged LZ4 frames (3i), uniform slots: every frame has the block slots of the largest chunk -- blocks of
+// bs = min(B, max_bytes) bytes (B: the level's block size), bpf = ceil(max_bytes / bs) of them -- so the layout is
+// frame_temp for nchunks * bpf blocks, then the derived block batch (a pointer and a size per block slot):
+//   staging slots | LZ4 sequence records, 8 bytes per block | block sizes | block offsets | block pointers | block sizes
+// (a batch of empty chunks is laid out with one 1-byte block slot per frame)
+struct Lz4fRaggedTemp {
+    FrameGeo g;
+    FrameTemp f;
+    size_t bptrs, bbytes, total;
+    int params;
+    LzhRaggedFrame slots(uint8_t* base) const {
+        return {f.slots(base), (const void**)(base + bptrs), (uint64_t*)(base + bbytes), g.bs, g.bpf, params};
+    }
+};
+static inline Lz4fRaggedTemp lz4f_ragged_temp(int params, size_t B, size_t max_bytes, size_t nchunks) {
+    Lz4fRaggedTemp t;
+    t.params = params;
+    t.g.F = max_bytes;
+    t.g.bs = std::max<size_t>(std::min(B, max_bytes), 1);
+    t.g.bpf = (uint32_t)std::max<size_t>((max_bytes + t.g.bs - 1) / t.g.bs, 1);
+    t.g.nframes = nchunks;
+    t.g.nblocks = nchunks * t.g.bpf;
+    t.f = frame_temp(t.g);
+    TempCursor c;
+    c.at = t.f.total;
+    t.bptrs = c.take(t.g.nblocks * 8);
+    t.bbytes = c.take(t.g.nblocks * 8, kGap);
+    t.total = c.at;
+    return t;
+}
+
 // ---- ragged compression, compact layout: every chunk's slots sized from its own size (LZ4 / snappy:
 // ragged_slots.h; zstd: its own size and the call's level, zstd_ragged_slots.h, where the uniform-slot chunk_temp
 // takes the worst of four levels):
@@ -277,6 +308,21 @@ static inline DecodeTemp ragged_decode_temp(size_t nchunks) {
     t.scan = c.take((nchunks + 1) * sizeof(uint64_t), kGap);
     t.need_scan = c.at;   // (the ragged call asks for the whole of `total`)
     t.desc = c.take(nchunks * 32, kGap);
+    t.total = c.at;
+    return t;
+}
+
+// ragged LZ4 frames (3i): the scanned offsets where ragged_decode_temp puts them, then the uniform frame decoder's
+// regions for nchunks frames of up to max_bytes: frame_maxbpf descriptor slots per frame | block statuses | frame statuses
+static inline DecodeTemp lz4f_ragged_decode_temp(size_t nchunks, size_t max_bytes) {
+    DecodeTemp t = {};
+    TempCursor c;
+    const size_t nd = nchunks * frame_maxbpf(LZH_CODEC_LZ4F, max_bytes);
+    t.scan = c.take((nchunks + 1) * sizeof(uint64_t), kGap);
+    t.need_scan = c.at;
+    t.desc = c.take(nd * 32);
+    t.bstat = c.take(nd * 4);
+    t.fstat = c.take(nchunks * 4, kGap);
     t.total = c.at;
     return t;
 }

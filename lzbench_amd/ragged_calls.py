@@ -1,4 +1,4 @@
-"""The ragged device calls of include/lzbench_hip.h 3b .. 3h as a table: one RaggedCall per async entry point.
+"""The ragged device calls of include/lzbench_hip.h 3b .. 3i as a table: one RaggedCall per async entry point.
 
 The calls share one argument list per direction and differ in a head (the arguments before the chunk arrays), in
 whether the batch's promised total follows max_chunk_bytes, and in their sizing calls.  The ctypes signatures of
@@ -52,7 +52,7 @@ class Sizing(_Call):
 class RaggedCall(_Call):
     symbol: str
     compress: bool                   # (else decompress)
-    family: str                      # RaggedCodec's variant: lz, lz4_dict, zstd, zstd_dfast, zstd_dict, zstd_dfast_dict
+    family: str                      # RaggedCodec's variant: lz, lz4_dict, zstd, zstd_dfast, zstd_dict, zstd_dfast_dict, lz4f
     head: Tuple[str, ...]            # of codec, level, dict, dict_bytes
     sizing: Sizing                   # the temp below which the call answers LZH_ESPACE
     promise: bool = False            # the compact layouts: the batch's promised total follows max_chunk_bytes
@@ -128,6 +128,9 @@ MORE_CALLS = (
     # 3h: zstd level 3 with a shared dictionary (the frames decode with 3f's call)
     _c("lzh_zstd_dfast_compress_ragged_dict_async", "zstd_dfast_dict", ("level",) + _DICT,
        Sizing("lzh_zstd_dfast_dict_compress_temp_bytes", ("level", "dict_bytes"))),
+    # 3i: LZ4 frames, a frame per chunk (level = LZH_LZ4F_PARAMS; independent blocks)
+    _c("lzh_lz4f_compress_ragged_async", "lz4f", ("level",), Sizing("lzh_lz4f_ragged_compress_temp_bytes", ("level",))),
+    _d("lzh_lz4f_decompress_ragged_async", "lz4f", (), Sizing("lzh_lz4f_ragged_decompress_temp_bytes")),
 )
 ALL_CALLS = RAGGED_CALLS + MORE_CALLS
 # RaggedCodec's lookup: (family, compact layout) -> the call
